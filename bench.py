@@ -1,7 +1,13 @@
 """Benchmark: skeleton-frames/sec (fwd+bwd) of the 10-layer ST-GCN (fcn_in + 9 StgcnLayers, as_is BN,
 Kt=9) at N=64 T=300 V=25 (BASELINE.json config 2), bf16 MFMA path, synthetic data.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--graph] [--config 2|4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--graph] [--config 2|4] [--full] [--dump-outputs DIR]
+
+A plain run does what the headline figure needs and no more: set-up, W warm-up steps, K timed steps (no event
+hooks installed, every launch on its unsplit path), the outputs of the last timed step written to DIR when
+--dump-outputs is given, and the JSON line (its secondary fields null).  --full adds the secondary measurements:
+the roofline brackets on every ROOF_EVERY-th timed step, the per-kernel table, the north_star layer rooflines and
+the CPU baseline.
 
 Config 2 (default): one step = forward of the whole model on one (64, 3, 300, 25) batch of windows + the
 reference loss (weighted CE + clamped temporal MSE, utils/loss.py:25-41, windows as the time axis like
@@ -23,7 +29,12 @@ num_subsegments; the units of all trials are dealt round-robin to the ranks
 (parallel.segment_units / units_for_rank).  A step = one unit per rank (64-65 windows staged on the GPU
 from the padded capture, window.hip), fwd + loss + bwd; the optimizer steps (and DDP all-reduces) every
 --accum steps, DDP.no_sync on the others (processor.py:531-564).
-Rank 0 prints ONE JSON line (metric/value/..., roofline, cpu_baseline).
+Rank 0 prints ONE JSON line (metric/value/...; with --full also roofline, kernels, layer rooflines, cpu_baseline).
+
+--dump-outputs DIR: rank 0 writes what the last timed step handed back, as float32 DIR/<name>.npy: the model's
+logits, the two loss terms (loss_ce, loss_mse), every parameter's gradient (grad.<parameter>) and its value after
+the optimizer step (param.<parameter>).  The seeds are fixed, so the same arguments give the same inputs in every
+run and two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -363,6 +374,40 @@ def trial_lengths(n_units, W=T_LEN, seg=N_BATCH, seed=2):
     return out
 
 
+def class_dist(dev):
+    """The synthetic class frequencies of the loss's CE weights (device generator, seed 12345)."""
+    gen = torch.Generator(device=dev).manual_seed(12345)
+    return torch.rand(CLASSES, device=dev, generator=gen) + 0.5
+
+
+def config2_batch(dev, rank):
+    """Config 2's resident batch of rank ``rank``: windows (64, 3, 300, 25) and labels (1, 64), device generator
+    seeded with the rank."""
+    gen = torch.Generator(device=dev).manual_seed(rank)
+    x = torch.randn(N_BATCH, 3, T_LEN, V_J, device=dev, generator=gen)
+    labels = torch.randint(0, CLASSES, (1, N_BATCH), device=dev, generator=gen)
+    return x, labels
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: ``arrays`` (name -> tensor) as float32 ``path/<name>.npy``.  Over DUMP_MAX_BYTES in all,
+    every array is cut to the same fraction of its (flattened) elements, picked by a generator seeded with 0."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    keep = min(1.0, 0.95 * DUMP_MAX_BYTES / max(total, 1))
+    rng = np.random.default_rng(0)
+    for name, a in arrays.items():
+        if keep < 1.0 and a.size > 1:
+            idx = np.sort(rng.choice(a.size, size=max(1, int(a.size * keep)), replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -378,10 +423,24 @@ def main():
     ap.add_argument("--sync-bn", action="store_true",
                     help="N > 1: SyncBatchNorm statistics over the ranks (syncbn.py) instead of the reference's "
                          "per-replica DataParallel statistics (the default)")
-    ap.add_argument("--kernel-steps", type=int, default=3,
-                    help="eager steps after the timed region whose kernel-wrapper launches are timed one by one "
-                         "(the `kernels` table); 0 = off")
+    ap.add_argument("--kernel-steps", type=int, default=None,
+                    help="with --full: eager steps after the timed region whose kernel-wrapper launches are timed "
+                         "one by one (the `kernels` table); default 3, 0 = off")
+    ap.add_argument("--full", action="store_true",
+                    help="also take the secondary measurements: roofline brackets inside the timed steps, the "
+                         "`kernels` table, the north_star layer rooflines, the CPU baseline (each still has its "
+                         "own switch above); without it only the headline figure is measured")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step (logits, loss terms, gradients, updated "
+                         "parameters) as float32 DIR/<name>.npy")
     args = ap.parse_args()
+    if not args.full:
+        if args.kernel_steps:
+            ap.error("--kernel-steps N > 0 (the `kernels` table) needs --full")
+        args.no_cpu_baseline = args.no_layer_roofline = True
+        args.kernel_steps = 0
+    elif args.kernel_steps is None:
+        args.kernel_steps = 3
     if args.config == 4 and args.graph:
         sys.exit("bench.py: --graph needs fixed shapes (config 2); config 4's units have 49-65 windows")
 
@@ -430,9 +489,7 @@ def main():
     # every parameter in ONE launch (csrc/adam.hip; test_gpu_optim.py); --torch-adam: torch's fused Adam
     opt = torch.optim.Adam(params, lr=5e-4, fused=True, capturable=args.graph) if args.torch_adam else \
         pkg.optim.Adam(params, lr=5e-4)
-    gen_t = torch.Generator(device=dev).manual_seed(12345)
-    class_dist = torch.rand(CLASSES, device=dev, generator=gen_t) + 0.5
-    crit = pkg.loss.Loss(dev, class_dist)
+    crit = pkg.loss.Loss(dev, class_dist(dev))
 
     # live timing of the roofline kernel (ROOF_TAGS: temporal-conv forward of the C=128/256 layers): HIP events
     # on the stream the kernel is launched on, with each launch's algorithmic flops.  ROCm refuses timing
@@ -448,17 +505,19 @@ def main():
         ev.record(torch.cuda.current_stream())
         events.append((tag, ev, work))
 
-    K.EVENT_HOOK = hook
+    if args.full:
+        K.EVENT_HOOK = hook
     frames_done = [0]
+    outs = {}  # what the latest step handed back (references only: nothing is copied or synchronised in a step)
 
     if args.config == 2:
-        gen = torch.Generator(device=dev).manual_seed(rank)
-        x = torch.randn(N_BATCH, 3, T_LEN, V_J, device=dev, generator=gen)
-        labels = torch.randint(0, CLASSES, (1, N_BATCH), device=dev, generator=gen)
+        x, labels = config2_batch(dev, rank)
 
         def fwd_loss():
-            pred = train_model(x).permute(2, 1, 0)  # (1, classes, windows): WindowSegment.mask_segment
+            logits = train_model(x)
+            pred = logits.permute(2, 1, 0)  # (1, classes, windows): WindowSegment.mask_segment
             ce, mse = crit(0, pred, labels)
+            outs.update(logits=logits, loss_ce=ce, loss_mse=mse)
             return ce + mse  # DDP / the flat all-reduce average over ranks: loss / batch_size (processor.py:538)
 
         def eager_step():
@@ -478,6 +537,8 @@ def main():
                 frames_done[0] += N_BATCH * T_LEN
         else:
             step = eager_step
+        # (never fewer than 2 warm-up steps: the first builds the workspaces and, with --graph, is the capture's
+        # eager step; `warmup` in the JSON line is the argument as given)
         for _ in range(max(args.warmup, 2)):
             step()
         torch.cuda.synchronize()
@@ -505,8 +566,10 @@ def main():
             cap, lab = caps[u.trial], labs[u.trial]
             last = (micro[0] + 1) % args.accum == 0
             with par.accumulate(train_model, last=last):
-                pred = train_model(pkg.segment.WindowBatch(cap, u.n0, u.nw, T_LEN)).permute(2, 1, 0)
+                logits = train_model(pkg.segment.WindowBatch(cap, u.n0, u.nw, T_LEN))
+                pred = logits.permute(2, 1, 0)
                 ce, mse = crit(u.i, pred, lab[:, u.y0:u.y1])
+                outs.update(logits=logits, loss_ce=ce, loss_mse=mse)
                 ((ce + mse) / u.count).backward()  # processor.py:392 (ce, mse / num_subsegments)
             if last:
                 opt.step()
@@ -518,16 +581,16 @@ def main():
             step()
         torch.cuda.synchronize()
 
-    timing["on"] = not args.graph
+    timing["on"] = args.full and not args.graph
     frames_done[0] = 0
     if world > 1:
         torch.distributed.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for k in range(args.steps):
-        # the roofline launches are bracketed on every ROOF_EVERY-th timed step (the 16 extra timing events of an
-        # instrumented step cost ~43 us; measured: 7.523 vs 7.480 ms/step with and without them on one box)
-        timing["on"] = not args.graph and k % ROOF_EVERY == 0
+        # --full: the roofline launches are bracketed on every ROOF_EVERY-th timed step (the 16 extra timing events
+        # of an instrumented step cost ~43 us; measured: 7.523 vs 7.480 ms/step with and without them on one box)
+        timing["on"] = args.full and not args.graph and k % ROOF_EVERY == 0
         K.EVENT_HOOK = hook if timing["on"] else None  # no hook: the wrappers take their unsplit launch paths
         step()
     torch.cuda.synchronize()
@@ -535,7 +598,15 @@ def main():
         torch.distributed.barrier()
     elapsed = time.perf_counter() - t0
     frames = frames_done[0]
-    if args.graph:
+    if args.dump_outputs and rank == 0 and args.steps > 0:  # before the instrumented steps below train further
+        arrays = dict(outs)
+        for name, p in model.named_parameters():
+            if p.requires_grad:
+                arrays["param." + name] = p
+                if p.grad is not None:
+                    arrays["grad." + name] = p.grad
+        dump_outputs(args.dump_outputs, arrays)
+    if args.graph and args.full:
         timing["on"] = True
         K.EVENT_HOOK = hook
         eager_step()
@@ -587,6 +658,14 @@ def main():
                         f"WindowSegment units of 64 windows x T=300 dealt round-robin to ranks, fwd + loss + bwd "
                         f"per unit, no_sync + Adam every {args.accum} units")
             metric = "skeleton-frames/sec (fwd+bwd), 10-layer ST-GCN DDP, long trials, windows of T=300 V=25"
+        tcn_roof = None
+        if args.full:
+            tcn_roof = {"kernel": "conv_wide_kernel<128,9,8,1,0,64> (persistent warp-specialised Kt=9 "
+                                  "stride-1 temporal conv fwd of the C=128 and C=256 layers, 4 launches/step)",
+                        "bound": "mfma", "achieved": round(achieved, 2) if achieved else None,
+                        "peak": BF16_DENSE_PEAK_TFLOPS, "unit": "TFLOP/s",
+                        "frac": round(achieved / BF16_DENSE_PEAK_TFLOPS, 4) if achieved else None,
+                        "traffic": traffic, "avg_launch_ms": round(k_ms, 4), "launches_timed": len(kt)}
         out = {
             "metric": metric,
             "value": round(value, 1), "unit": "skeleton-frames/s", "per_gpu": round(value / world, 1),
@@ -601,13 +680,9 @@ def main():
                        "launch": "eager" if not args.graph else (
                            "hip-graph replay (fwd+bwd | Adam)" if world == 1 else
                            "hip-graph replay (fwd+bwd with captured 4 MB bucket all-reduces + Adam, one graph)")},
+            "full": args.full,  # False: the fields below were not measured (null)
             "roofline": roof,
-            "roofline_tcn_fwd": {"kernel": "conv_wide_kernel<128,9,8,1,0,64> (persistent warp-specialised Kt=9 "
-                                           "stride-1 temporal conv fwd of the C=128 and C=256 layers, 4 launches/step)",
-                         "bound": "mfma", "achieved": round(achieved, 2) if achieved else None,
-                         "peak": BF16_DENSE_PEAK_TFLOPS, "unit": "TFLOP/s",
-                         "frac": round(achieved / BF16_DENSE_PEAK_TFLOPS, 4) if achieved else None,
-                         "traffic": traffic, "avg_launch_ms": round(k_ms, 4), "launches_timed": len(kt)},
+            "roofline_tcn_fwd": tcn_roof,
             "kernels": ktable,
             "layer_roofline": lroof,
             "layer_roofline_ln": lroof_ln,

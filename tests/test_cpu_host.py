@@ -109,6 +109,26 @@ def test_bench_multi_gpu_launch_rejected_cleanly_without_devices():
     assert r.returncode != 0 and "WORLD_SIZE=3" in r.stderr and "Traceback" not in r.stderr
 
 
+def test_bench_dump_outputs_float32_and_bounded(tmp_path, monkeypatch):
+    """bench.py --dump-outputs writes float32 .npy files; over the size limit every array is cut to the same
+    fixed (seed 0) sample of its elements, so two runs keep the same ones."""
+    import bench
+    arrays = {"a": torch.arange(1000, dtype=torch.float64).reshape(10, 100),
+              "b.w": torch.ones(7, dtype=torch.bfloat16), "s": torch.tensor(2.5)}
+    bench.dump_outputs(str(tmp_path / "whole"), arrays)
+    got = {k: np.load(tmp_path / "whole" / f"{k}.npy", allow_pickle=False) for k in arrays}
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert got["a"].shape == (10, 100) and np.array_equal(got["a"].ravel(), np.arange(1000)) and got["s"] == 2.5
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 1024)
+    cut = []
+    for d in ("cut1", "cut2"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+        cut.append({k: np.load(tmp_path / d / f"{k}.npy", allow_pickle=False) for k in arrays})
+    assert sum(v.nbytes for v in cut[0].values()) <= 1024
+    assert 0 < cut[0]["a"].size < 1000 and set(cut[0]["a"]) <= set(range(1000)) and cut[0]["s"] == 2.5
+    assert all(np.array_equal(cut[0][k], cut[1][k]) for k in arrays)
+
+
 class _FakeDev:
     def __init__(self, i):
         self.index = i
