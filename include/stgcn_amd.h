@@ -31,8 +31,9 @@ extern "C" {
  *      fields n1_scale / n1_shift / stats / ln / g_in / g_in_ld and stgcn_layer_fused_row_blocks removed);
  *   4: round 6 (stgcn_rt_frame + stgcn_rt_layer / stgcn_rt_frame_desc: the RT per-frame step in one launch;
  *      stgcn_gconv_wgrad_desc gained phase);
- *   5: round 6 (stgcn_bn_merge: one (count, mean, M2) entry per channel, the SyncBatchNorm exchange unit). */
-#define STGCN_ABI_VERSION 5
+ *   5: round 6 (stgcn_bn_merge: one (count, mean, M2) entry per channel, the SyncBatchNorm exchange unit);
+ *   6: stgcn_co_* + stgcn_co_layer: CoST-GCN per-frame inference (co_frame.hip). */
+#define STGCN_ABI_VERSION 6
 
 /* Implicit-GEMM (Kt x 1) row convolution; see conv_rows.hip for the exact contract.
  * Replaces: nn.Conv2d tcn.2 (models/stgcn/stgcn.py:154-159), residual.0 (stgcn.py:165-170),
@@ -475,6 +476,61 @@ typedef struct {
   stgcn_rt_layer layers[STGCN_RT_MAX_LAYERS];
 } stgcn_rt_frame_desc;
 int stgcn_rt_frame(const stgcn_rt_frame_desc* d, void* stream);
+
+/* CoST-GCN per-frame inference (models/costgcn/costgcn.py:192-211; co_frame.hip), batch 1, one frame per call,
+ * LayerNorm layers.  A layer keeps a ring of the last fifo = S*(Kt-1)+1 frames of ReLU(LN1(gcn(x))) (tcn.0 is per
+ * frame, so its result is cached; an empty FIFO normalises to ReLU(tcn.0.bias), which the CALLER writes into every
+ * slot before the first frame) and a ring of the last R = Kt/2+1 residual frames (zeros at the start), and every
+ * frame evaluates the Kt-tap temporal convolution with dilation S over the ring: tap k meets the frame of age k*S.
+ * One frame of one layer is the four calls, in this order, on one stream:
+ *   stgcn_co_gcn    : z_buf = gcn(x, A) (w [P*Cout][Cin], bias2d [V][Cout] = the conv bias through A, or NULL),
+ *                     r_buf = wr x + br (res_mode 2: the residual conv has a bias, costgcn.py:178-181)
+ *   stgcn_co_push   : ring[head'] = ReLU(LN1(z_buf)) (dtype elements), res_ring[rhead'] = x (res_mode 1) |
+ *                     LN_r(r_buf) (2), head' = (idx[0] + fifo - 1) % fifo, rhead' = (idx[1] + R - 1) % R
+ *   stgcn_co_taps   : partial[s][v][co] = sum over K split s of wt . ring, K = Kt*Cout split into `splits` ranges of
+ *                     16-element steps, grid (Cout/32 column tiles) x (splits); MFMA, fp32 accumulation
+ *   stgcn_co_finish : y = relu(LN2(bt + sum_s partial[s]) + res_ring[(rhead' + Kt/2) % R]) (no residual term for
+ *                     res_mode 0); idx = (head', rhead')
+ * Hand-offs are kernel boundaries; no atomics: a stream replays bit-identically from the same ring state.
+ * Rows are [V][C] fp32; LayerNorm affines are the (C,1,V) parameters as stored (element c*V + v); statistics per
+ * frame over C*V values, unbiased variance, eps 1e-5.  dtype (0 fp32 | 1 bf16) is the element type of ring and wt
+ * only.  wt: stgcn_co_pack_weight's image of the Conv2d weight [Cout][Cout][Kt] (stgcn_co_pack_elems elements).
+ * splits: 0 = chosen so that the grid covers every CU (stgcn_co_splits returns the count used);
+ * partial: stgcn_co_workspace bytes.
+ * 2 <= V <= 32, P <= 3, channels % 4 == 0 and <= 256, odd Kt <= 69, S in {1, 2}, res_mode 1 needs Cin == Cout;
+ * anything else (or a NULL required pointer) returns 1 before any launch. */
+typedef struct {
+  int V, Cin, Cout, P, Kt, S, res_mode, dtype, splits, pad_;
+  const float* x;       /* [V][Cin] the layer's input frame */
+  const float* A;       /* [P][V][V] graph * importance */
+  const float* w;       /* [P*Cout][Cin] gcn.conv */
+  const float* bias2d;  /* [V][Cout] or NULL */
+  const float* wr;      /* [Cout][Cin] residual.0 (res_mode 2) */
+  const float* br;      /* [Cout] or NULL */
+  const float* ln1_w;   /* tcn.0 */
+  const float* ln1_b;
+  const float* ln2_w;   /* tcn.3 */
+  const float* ln2_b;
+  const float* lnr_w;   /* residual.1 (res_mode 2) */
+  const float* lnr_b;
+  const void* wt;       /* packed tcn.2 weight, dtype elements */
+  const float* bt;      /* [Cout] tcn.2 bias or NULL */
+  void* ring;           /* [fifo][V][Cout] dtype elements */
+  float* res_ring;      /* [Kt/2+1][V][Cout] */
+  int* idx;             /* int[2]: slot of the newest frame in ring, res_ring */
+  float* z_buf;         /* [V][Cout] */
+  float* r_buf;         /* [V][Cout] (res_mode 2) */
+  float* partial;       /* [splits][V][Cout] */
+  float* y;             /* [V][Cout] */
+} stgcn_co_layer;
+long stgcn_co_pack_elems(int Cout, int C, int Kt);
+int stgcn_co_pack_weight(const float* w, int Cout, int C, int Kt, void* dst, int dtype, void* stream);
+int stgcn_co_splits(const stgcn_co_layer* d, void* stream);
+long stgcn_co_workspace(const stgcn_co_layer* d, void* stream);
+int stgcn_co_gcn(const stgcn_co_layer* d, void* stream);
+int stgcn_co_push(const stgcn_co_layer* d, void* stream);
+int stgcn_co_taps(const stgcn_co_layer* d, void* stream);
+int stgcn_co_finish(const stgcn_co_layer* d, void* stream);
 
 /* Window staging (window.hip): the first activation of a batch of sliding windows
  * (WindowSegment, utils/segment_generator.py:132-145) computed from the padded capture without forming the

@@ -24,3 +24,8 @@ try:
     MODELS["aa-gcn"] = AaGcn
 except ImportError:  # pragma: no cover
     pass
+try:
+    from .costgcn import Model as CoStgcn  # noqa: F401
+    MODELS["co-st-gcn"] = CoStgcn
+except ImportError:  # pragma: no cover
+    pass

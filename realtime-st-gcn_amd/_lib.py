@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("STGCN_LIB") or os.path.join(_HERE, "lib", "libstgcn_amd.so")  # STGCN_LIB: A/B builds
 
 # the STGCN_ABI_VERSION of include/stgcn_amd.h these bindings mirror (test_cpu_host checks the two agree)
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 _ERR = {1: "bad shape/arguments", 2: "unsupported dtype", 3: "HIP launch error"}
 
@@ -102,6 +102,13 @@ class RtFrameDesc(ctypes.Structure):
                [("layers", RtLayer * RT_MAX_LAYERS)]
 
 
+class CoLayer(ctypes.Structure):  # stgcn_co_layer
+    _fields_ = [(n, c_int) for n in ("V", "Cin", "Cout", "P", "Kt", "S", "res_mode", "dtype", "splits", "pad_")] + \
+               [(n, c_void_p) for n in ("x", "A", "w", "bias2d", "wr", "br", "ln1_w", "ln1_b", "ln2_w", "ln2_b",
+                                        "lnr_w", "lnr_b", "wt", "bt", "ring", "res_ring", "idx", "z_buf", "r_buf",
+                                        "partial", "y")]
+
+
 # name -> (restype, argtypes)
 _SIGS = {
     "stgcn_abi_version": (c_int, []),
@@ -182,6 +189,14 @@ _SIGS = {
                                     c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "stgcn_rt_frame_out": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "stgcn_rt_frame": (c_int, [ctypes.POINTER(RtFrameDesc), c_void_p]),
+    "stgcn_co_pack_elems": (c_long, [c_int, c_int, c_int]),
+    "stgcn_co_pack_weight": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "stgcn_co_splits": (c_int, [ctypes.POINTER(CoLayer), c_void_p]),
+    "stgcn_co_workspace": (c_long, [ctypes.POINTER(CoLayer), c_void_p]),
+    "stgcn_co_gcn": (c_int, [ctypes.POINTER(CoLayer), c_void_p]),
+    "stgcn_co_push": (c_int, [ctypes.POINTER(CoLayer), c_void_p]),
+    "stgcn_co_taps": (c_int, [ctypes.POINTER(CoLayer), c_void_p]),
+    "stgcn_co_finish": (c_int, [ctypes.POINTER(CoLayer), c_void_p]),
     "stgcn_window_stat_blocks": (c_int, [c_int, c_int]),
     "stgcn_window_stats": (c_int, [c_void_p] + [c_int] * 7 + [c_float, c_void_p, c_void_p]),
     "stgcn_window_expand": (c_int, [c_void_p] + [c_int] * 7 + [c_void_p] * 5 + [c_int, c_void_p, c_int, c_int,

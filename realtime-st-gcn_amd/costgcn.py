@@ -1,0 +1,227 @@
+"""CoST-GCN (models/costgcn/costgcn.py): continual per-frame ST-GCN inference on the HIP kernels (co_frame.hip).
+
+``Model(**arch)`` reads ``arch['st-gcn']`` like the reference and keeps the ST-GCN parameter names
+(``gcn_networks.i.gcn.conv``, ``.tcn.0``, ``.tcn.2``, ``.tcn.3``, ``.residual.0``, ``.residual.1``,
+``edge_importance.i``, buffer ``A``): a checkpoint of ``MODELS['st-gcn']`` loads with ``strict=True`` and back.
+
+forward(x (1, in_feat, 1, V)) -> (1, num_classes, 1), one frame per call.  Every layer keeps the last
+``S*(Kt-1)+1`` frames of its graph conv and evaluates the learned Kt-tap temporal conv (dilation S, tap 0 on the
+newest frame) over them each frame (costgcn.py:192-211); the residual is delayed by Kt//2 frames.  The reference
+holds those FIFOs in CPU tensors; here they are device rings the kernels update, so one captured HIP graph of a
+frame replays a stream.  The activation ring caches ReLU(tcn.0(z)) (tcn.0 is a per-frame LayerNorm), so an empty
+FIFO is ``ReLU(tcn.0.bias)`` in every slot, not zero: the ring content depends on a parameter, and the rings (and
+the weight packs) are rebuilt whenever parameters may have changed — ``load_state_dict``, ``train()`` /
+``eval()``, a device or dtype move, or an in-place parameter update seen by the version counters.  A rebuild
+restarts the stream.  ``reset_state()`` restarts it explicitly and keeps the buffers (a captured graph stays valid).
+
+Scope: LayerNorm only (the reference's BatchNorm variant takes statistics over whatever the FIFO holds), batch 1,
+inference only, in_feat 3, V <= 32, P <= 3, channels % 4 == 0 and <= 256, odd Kt <= 69, stride 1 or 2.
+"""
+from __future__ import annotations
+
+import torch
+import torch.nn as nn
+
+from . import layer_fn as LF
+from . import native as K
+from .graph import Graph
+from .modules import ConvTemporalGraphical, LayerNorm, resolve_dtype
+
+
+class CoStgcnLayer(nn.Module):
+    """Parameter holder of one continual layer (costgcn.py:106-189); the arithmetic runs in Model.forward."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, partitions, num_joints, stride=1, dilation=1, dropout=0,
+                 residual=True, normalization="LayerNorm"):
+        super().__init__()
+        assert len(kernel_size) == 2
+        assert kernel_size[0] % 2 == 1
+        if normalization != "LayerNorm":
+            raise NotImplementedError("stgcn_amd: co-st-gcn supports normalization='LayerNorm' only (the reference's "
+                                      "BatchNorm variant takes batch statistics over the FIFO content)")
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.gamma = kernel_size[0]
+        self.stride = stride
+        self.fifo_size = stride * (self.gamma - 1) + 1
+        self.is_residual = residual
+        self.is_residual_conv = residual and not ((in_channels == out_channels) and (stride == 1))
+        self.gcn = ConvTemporalGraphical(in_channels, out_channels, kernel_size[1], partitions)
+        self.tcn = nn.Sequential(
+            LayerNorm([out_channels, 1, num_joints]),
+            nn.ReLU(inplace=True),
+            nn.Conv2d(out_channels, out_channels, (kernel_size[0], 1), dilation=(stride, 1), padding="valid"),
+            LayerNorm([out_channels, 1, num_joints]),
+            nn.Dropout(dropout, inplace=True))
+        if self.is_residual_conv:
+            self.residual = nn.Sequential(nn.Conv2d(in_channels, out_channels, kernel_size=1),
+                                          LayerNorm([out_channels, 1, num_joints]))
+        else:
+            self.residual = nn.Identity()
+
+
+class Model(nn.Module):
+    def __init__(self, rank=None, **kwargs):
+        super().__init__()
+        conf = kwargs["st-gcn"]
+        if kwargs["normalization"] != "LayerNorm":
+            raise NotImplementedError("stgcn_amd: co-st-gcn supports normalization='LayerNorm' only (the reference's "
+                                      "BatchNorm variant takes batch statistics over the FIFO content)")
+        self.graph = Graph(strategy=kwargs["strategy"], **kwargs["graph"])
+        A = torch.tensor(self.graph.A, dtype=torch.float32, requires_grad=False).contiguous()
+        self.register_buffer("A", A)
+        kernel_size = (conf["kernel"], kwargs["graph"]["num_node"])
+        dilation = conf.get("dilation", [1] * conf["layers"])
+        self.norm_in = LayerNorm([kwargs["in_feat"], 1, A.size(1)])
+        self.fcn_in = nn.Conv2d(in_channels=conf["in_feat"], out_channels=conf["in_ch"][0], kernel_size=1)
+        self.gcn_networks = nn.ModuleList([
+            CoStgcnLayer(in_channels=conf["in_ch"][i], out_channels=conf["out_ch"][i], kernel_size=kernel_size,
+                         partitions=A.size(0), num_joints=A.size(1), stride=conf["stride"][i], dilation=dilation[i],
+                         residual=not not conf["residual"][i], dropout=conf["dropout"][i],
+                         normalization=kwargs["normalization"])
+            for i in range(conf["layers"])])
+        if conf["importance"]:
+            self.edge_importance = nn.ParameterList([nn.Parameter(torch.ones(self.A.size()))
+                                                     for _ in self.gcn_networks])
+        else:
+            self.edge_importance = [1] * len(self.gcn_networks)
+        self.fcn_out = nn.Conv2d(conf["out_ch"][-1], out_channels=kwargs["num_classes"], kernel_size=1)
+        self.compute_dtype = torch.float32
+        self.k_splits = 0  # stgcn_co_layer.splits of every layer: 0 = the library's choice (tests force others)
+        self._plan = None  # (key, _Plan): descriptors, weight packs and ring state; never part of the state_dict
+
+    # ------------------------------------------------------------------ whatever may change a parameter drops the plan
+    def _drop(self):
+        self._plan = None
+
+    def train(self, mode: bool = True):
+        self._drop()
+        return super().train(mode)
+
+    def load_state_dict(self, *args, **kwargs):
+        self._drop()
+        return super().load_state_dict(*args, **kwargs)
+
+    def _apply(self, fn, *args, **kwargs):
+        self._drop()
+        return super()._apply(fn, *args, **kwargs)
+
+    def set_compute_dtype(self, dtype):
+        """fp32, or bf16 tap weights and activation ring (fp32 accumulation; norms, residual ring and layer outputs
+        stay fp32).  Restarts the stream."""
+        self.compute_dtype = resolve_dtype(dtype)
+        self._drop()
+        return self
+
+    def set_k_splits(self, n: int):
+        """Force the tap kernel's K-split count (0: chosen by the library).  Restarts the stream."""
+        self.k_splits = int(n)
+        self._drop()
+        return self
+
+    # ------------------------------------------------------------------ plan: packs + rings + descriptors
+    def _key(self):
+        ts = [self.A] + list(self.parameters())
+        return (self.compute_dtype, self.k_splits) + tuple((t.data_ptr(), t._version) for t in ts)
+
+    def _ring_init(self, layer, ring, res_ring, idx):
+        """An empty FIFO as the ring caches it: ReLU(LN1(0)) = ReLU(tcn.0.bias) in every slot; residuals zero."""
+        V, C = self.A.shape[-1], layer.out_channels
+        b = torch.relu(layer.tcn[0].bias.detach().float()).reshape(C, V).t()
+        ring.copy_(b.unsqueeze(0).expand_as(ring))
+        res_ring.zero_()
+        idx.zero_()
+
+    def _build(self):
+        dev, dt = self.A.device, self.compute_dtype
+        K.L.require_device(self.A)
+        V, P = self.A.shape[-1], self.A.shape[0]
+        if len(self.gcn_networks) > K.L.RT_MAX_LAYERS:
+            raise RuntimeError(f"stgcn_amd: co-st-gcn supports at most {K.L.RT_MAX_LAYERS} layers")
+        if self.fcn_in.in_channels != 3 or self.norm_in.weight.shape[0] != 3:
+            raise RuntimeError("stgcn_amd: co-st-gcn per-frame input head takes in_feat == 3")
+        keep, descs, state = [], [], []
+
+        def p(t):
+            keep.append(t)
+            return t.data_ptr()
+
+        def f32(t):
+            return t.detach().float().contiguous()
+
+        for i, l in enumerate(self.gcn_networks):
+            Cin, C, Kt = l.in_channels, l.out_channels, l.gamma
+            A_eff = f32(self.A * self.edge_importance[i])
+            d = K.L.CoLayer()
+            d.V, d.Cin, d.Cout, d.P, d.Kt, d.S = V, Cin, C, P, Kt, l.stride
+            d.res_mode = 2 if l.is_residual_conv else (1 if l.is_residual else 0)
+            d.dtype, d.splits = K.L.dtype_code(dt), self.k_splits
+            d.splits, nbytes = K.co_workspace(d)  # raises on shapes the kernels do not take
+            d.A = p(A_eff)
+            d.w = p(f32(l.gcn.conv.weight).reshape(P * C, Cin))
+            d.bias2d = p(K.gcn_bias(A_eff, f32(l.gcn.conv.bias), 1, C))
+            if l.is_residual_conv:
+                d.wr, d.br = p(f32(l.residual[0].weight).reshape(C, Cin)), p(f32(l.residual[0].bias))
+                d.lnr_w, d.lnr_b = p(LF._flat_ln(l.residual[1].weight)), p(LF._flat_ln(l.residual[1].bias))
+                d.r_buf = p(torch.empty(V * C, dtype=torch.float32, device=dev))
+            d.ln1_w, d.ln1_b = p(LF._flat_ln(l.tcn[0].weight)), p(LF._flat_ln(l.tcn[0].bias))
+            d.ln2_w, d.ln2_b = p(LF._flat_ln(l.tcn[3].weight)), p(LF._flat_ln(l.tcn[3].bias))
+            d.wt = p(K.co_pack_weight(l.tcn[2].weight, dt))
+            d.bt = p(f32(l.tcn[2].bias))
+            ring = torch.empty((l.fifo_size, V, C), dtype=dt, device=dev)
+            res_ring = torch.empty((Kt // 2 + 1, V, C), dtype=torch.float32, device=dev)
+            idx = torch.empty(2, dtype=torch.int32, device=dev)
+            self._ring_init(l, ring, res_ring, idx)
+            state.append((l, ring, res_ring, idx))
+            d.ring, d.res_ring, d.idx = p(ring), p(res_ring), p(idx)
+            d.z_buf = p(torch.empty(V * C, dtype=torch.float32, device=dev))
+            d.partial = p(K._workspace(nbytes, dev))
+            y = K.cl_empty(1, C, 1, V, torch.float32, dev)
+            d.y = p(y)
+            if descs:
+                d.x = descs[-1].y
+            descs.append(d)
+        head = (LF._flat_ln(self.norm_in.weight), LF._flat_ln(self.norm_in.bias),
+                f32(self.fcn_in.weight).reshape(self.fcn_in.out_channels, -1), f32(self.fcn_in.bias),
+                f32(self.fcn_out.weight).reshape(self.fcn_out.out_channels, -1), f32(self.fcn_out.bias))
+        return {"descs": descs, "state": state, "keep": keep, "head": head, "y": keep[-1]}
+
+    def _ensure(self):
+        key = self._key()
+        pk = self._plan
+        if pk is None or pk[0] != key:
+            with K.device_of(self.A):
+                pk = (key, self._build())
+            self._plan = pk
+            return pk[1], True
+        return pk[1], False
+
+    def reset_state(self):
+        """Restart the stream: rings back to an empty FIFO (ReLU(tcn.0.bias) / zero), indices cleared.  Buffers are
+        kept when the parameters are unchanged, so a captured graph of a frame stays valid."""
+        plan, fresh = self._ensure()
+        if not fresh:
+            for l, ring, res_ring, idx in plan["state"]:
+                self._ring_init(l, ring, res_ring, idx)
+
+    @torch.no_grad()
+    def _frame(self, x):
+        plan, _ = self._ensure()
+        g_in, b_in, w_in, bias_in, w_out, bias_out = plan["head"]
+        y = K.rt_frame_in(x, g_in, b_in, w_in, bias_in)
+        descs = plan["descs"]
+        descs[0].x = y.data_ptr()
+        for d in descs:
+            K.co_layer_frame(d)
+        return K.rt_frame_out(plan["y"], w_out, bias_out)
+
+    def forward(self, x):
+        if torch.is_grad_enabled() and any(q.requires_grad for q in self.parameters()):
+            raise RuntimeError("stgcn_amd: co-st-gcn is inference only (call under torch.no_grad() or freeze the "
+                               "parameters)")
+        if x.dim() != 4 or x.shape[0] != 1 or x.shape[2] != 1 or x.shape[3] != self.A.shape[-1]:
+            raise RuntimeError("stgcn_amd: co-st-gcn processes one frame of batch 1: x (1, in_feat, 1, V), got "
+                               f"{tuple(x.shape)}")
+        return self._frame(x)
+
+    def prepare_benchmark(self, arch_conf):
+        return arch_conf

@@ -109,6 +109,14 @@ int rt_norm_launch(const float* a, const float* g, const float* b, int res_mode,
                    const float* br, int V, int C, int* idx, int fifo_size, int S, float* y, hipStream_t s);
 int rt_out_launch(const float* x, int V, int C, const float* W, const float* bias, int K, float* out, hipStream_t s);
 int rt_frame_launch(const stgcn_rt_frame_desc& d, hipStream_t s);
+int co_check(const stgcn_co_layer& d, bool shapes_only);
+int co_num_splits(const stgcn_co_layer& d, hipStream_t s);
+long co_pack_elems(int Cout, int C, int Kt);
+int co_pack_launch(const float* w, int Cout, int C, int Kt, void* dst, int dtype, hipStream_t s);
+int co_gcn_launch(const stgcn_co_layer& d, hipStream_t s);
+int co_push_launch(const stgcn_co_layer& d, hipStream_t s);
+int co_taps_launch(const stgcn_co_layer& d, hipStream_t s);
+int co_finish_launch(const stgcn_co_layer& d, hipStream_t s);
 int window_stat_blocks_launch(int nw, int W);
 int window_stats_launch(const float* x, int Cin, int Lp, int V, int W, int n0, int nw, int mode, float eps, float* out,
                         hipStream_t s);
@@ -444,6 +452,29 @@ int stgcn_rt_frame_out(const float* x, int V, int C, const float* w, const float
 int stgcn_rt_frame(const stgcn_rt_frame_desc* d, void* stream) {
   return d ? rt_frame_launch(*d, STREAM(stream)) : STGCN_EBADSHAPE;
 }
+
+long stgcn_co_pack_elems(int Cout, int C, int Kt) { return co_pack_elems(Cout, C, Kt); }
+int stgcn_co_pack_weight(const float* w, int Cout, int C, int Kt, void* dst, int dtype, void* stream) {
+  return co_pack_launch(w, Cout, C, Kt, dst, dtype, STREAM(stream));
+}
+int stgcn_co_splits(const stgcn_co_layer* d, void* stream) {
+  return d && co_check(*d, true) == STGCN_OK ? co_num_splits(*d, STREAM(stream)) : -1;
+}
+long stgcn_co_workspace(const stgcn_co_layer* d, void* stream) {
+  if (!d || co_check(*d, true) != STGCN_OK) return -1;
+  return (long)co_num_splits(*d, STREAM(stream)) * d->V * d->Cout * (long)sizeof(float);
+}
+#define CO_ENTRY(name, launch)                                  \
+  int name(const stgcn_co_layer* d, void* stream) {             \
+    if (!d) return STGCN_EBADSHAPE;                             \
+    const int rc = co_check(*d, false);                         \
+    return rc != STGCN_OK ? rc : launch(*d, STREAM(stream));    \
+  }
+CO_ENTRY(stgcn_co_gcn, co_gcn_launch)
+CO_ENTRY(stgcn_co_push, co_push_launch)
+CO_ENTRY(stgcn_co_taps, co_taps_launch)
+CO_ENTRY(stgcn_co_finish, co_finish_launch)
+#undef CO_ENTRY
 
 int stgcn_window_stat_blocks(int nw, int W) { return window_stat_blocks_launch(nw, W); }
 int stgcn_window_stats(const float* x, int Cin, int Lp, int V, int W, int n0, int nw, int mode, float eps, float* out,

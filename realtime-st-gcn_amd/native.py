@@ -1045,6 +1045,39 @@ def rt_frame(desc, x, out):
     return out
 
 
+# ------------------------------------------------------------------------------ CoST-GCN per-frame (co_frame.hip)
+def co_pack_weight(w, dtype):
+    """tcn.2 weight (Cout, C, Kt, 1) -> the tap kernel's [tile][k-step][lane][8] image in ``dtype``."""
+    L.require_device(w)
+    Cout, C, Kt = w.shape[0], w.shape[1], w.shape[2]
+    n = L.lib().stgcn_co_pack_elems(Cout, C, Kt)
+    if n < 0:
+        raise RuntimeError(f"stgcn_amd: co_pack_weight: unsupported shape Cout={Cout} C={C} Kt={Kt}")
+    out = torch.empty(n, dtype=dtype, device=w.device)
+    L.check(L.lib().stgcn_co_pack_weight(_f32c(w.detach()).data_ptr(), Cout, C, Kt, out.data_ptr(),
+                                         L.dtype_code(dtype), L.stream()), "co_pack_weight")
+    return out
+
+
+def co_workspace(desc):
+    """(K-split count, bytes of the split partials) of a stgcn_co_layer descriptor; raises on unsupported shapes."""
+    n = L.lib().stgcn_co_splits(ctypes.byref(desc), L.stream())
+    nbytes = L.lib().stgcn_co_workspace(ctypes.byref(desc), L.stream())
+    if n < 1 or nbytes < 0:
+        raise RuntimeError("stgcn_amd: co-st-gcn layer shape not supported (V <= 32, P <= 3, C % 4 == 0, C <= 256, "
+                           "odd Kt <= 69, stride 1 or 2)")
+    return n, nbytes
+
+
+def co_layer_frame(desc):
+    """One frame of one CoST-GCN layer: the four launches of stgcn_co_layer ``desc``."""
+    lib, d, s = L.lib(), ctypes.byref(desc), L.stream()
+    L.check(lib.stgcn_co_gcn(d, s), "co_gcn")
+    L.check(lib.stgcn_co_push(d, s), "co_push")
+    L.check(lib.stgcn_co_taps(d, s), "co_taps")
+    L.check(lib.stgcn_co_finish(d, s), "co_finish")
+
+
 # ------------------------------------------------------------------------------ window staging (window.hip)
 def _capture(x):
     """(1, Cin, Lp, V) padded capture -> contiguous fp32 [Cin][Lp][V] on the device."""

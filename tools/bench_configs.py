@@ -12,7 +12,12 @@ f1:       window staging (config/pku-mmd/ln/stgcn_local.json: receptive_field 50
           order (unfold the windows, then norm_in and fcn_in on the copies — our HIP kernels on both sides),
           fwd and bwd, BatchNorm and LayerNorm, bf16.
 
-    python tools/bench_configs.py [--frames 2000] [--steps 10] [--only 3|5|ln|f1]
+co:       CoST-GCN continual inference (config/pku-mmd/ln/costgcn_local.json widths and strides, LN) at Kt = 9
+          and Kt = 69, fp32 and bf16: per-frame p50 / p90 over graph-replayed frames after the FIFOs have filled,
+          the tap-weight bytes one frame reads and the HBM-peak fraction they imply, and the plain-PyTorch
+          restatement (tests/costgcn_ref.py) timed on the host.  Only with --only co.
+
+    python tools/bench_configs.py [--frames 2000] [--steps 10] [--only 3|5|ln|f1|co]
 Prints one JSON line per config.
 """
 import argparse
@@ -271,6 +276,78 @@ def staging(P, dev, reps=50):
     return out
 
 
+HBM_PEAK_BPS = 8.0e12  # MI355X HBM3E specification peak
+
+
+def costgcn(P, dev, kernel, dtype, frames=256, cpu_frames=3):
+    """One line of the co-st-gcn table: the reference schedule at temporal kernel ``kernel`` in ``dtype``."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from costgcn_ref import costgcn_stream
+    arch = {"strategy": "spatial", "in_feat": 3, "stages": 1, "kernel": kernel, "output_type": "logits",
+            "normalization": "LayerNorm", "num_classes": 52, "graph": P.PKU_MMD,
+            "st-gcn": dict(LAYERS, kernel=kernel, latency=False, importance=True, in_feat=3, stages=1,
+                           dilation=[1] * 9)}
+    torch.manual_seed(0)
+    m = P.MODELS["co-st-gcn"](rank=None, **arch)
+    sd = {k: v.clone() for k, v in m.state_dict().items()}
+    m = m.to(dev).eval().set_compute_dtype(dtype)
+    fill = max(arch["st-gcn"]["stride"]) * (kernel - 1) + 1
+    gen = torch.Generator(device=dev).manual_seed(3)
+    stream = torch.randn(fill + frames + 8, 1, 3, 1, 25, device=dev, generator=gen)
+    es = 2 if dtype == "bf16" else 4
+    wbytes = sum(kernel * c * c * es for c in LAYERS["out_ch"])
+    with torch.no_grad():
+        x_static = torch.zeros_like(stream[0])
+        for i in range(3):
+            x_static.copy_(stream[i])
+            m(x_static)
+        m.reset_state()
+        g = torch.cuda.CUDAGraph()
+        s_ = torch.cuda.Stream()
+        s_.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s_):
+            with torch.cuda.graph(g):
+                m(x_static)
+        torch.cuda.current_stream().wait_stream(s_)
+        m.reset_state()
+        for i in range(fill):  # fill every FIFO
+            x_static.copy_(stream[i])
+            g.replay()
+        lat = []
+        for i in range(frames):
+            x_static.copy_(stream[fill + i])
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            g.replay()
+            torch.cuda.synchronize()
+            lat.append(time.perf_counter() - t0)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(frames):
+            g.replay()
+        e1.record()
+        torch.cuda.synchronize()
+        dev_ms = e0.elapsed_time(e1) / frames
+        splits = [d.splits for d in m._plan[1]["descs"]]
+        # the restatement on the host (the reference's own arithmetic: FIFOs in CPU tensors)
+        xc = stream[:cpu_frames + 1, 0].permute(1, 2, 0, 3).reshape(1, 3, cpu_frames + 1, 25).cpu()
+        costgcn_stream(xc[:, :, :1], sd, arch, sd["A"], round_bf16=dtype == "bf16")
+        t0 = time.perf_counter()
+        costgcn_stream(xc[:, :, 1:], sd, arch, sd["A"], round_bf16=dtype == "bf16")
+        cpu_ms = 1e3 * (time.perf_counter() - t0) / cpu_frames
+    return {"config": f"co-st-gcn continual inference (ln/costgcn_local.json widths, LN, 9 layers), Kt={kernel}, "
+                      "1 frame (1,3,1,25)",
+            "metric": "per-frame latency, HIP graph replay, FIFOs full", "unit": "ms", "dtype": dtype,
+            "frames": frames, "p50_ms": round(1e3 * pct(lat, 0.5), 4), "p90_ms": round(1e3 * pct(lat, 0.9), 4),
+            "device_ms_per_frame": round(dev_ms, 4), "k_splits": splits,
+            "tap_weight_bytes_per_frame": wbytes,
+            "hbm_peak_fraction": round(wbytes / (dev_ms * 1e-3) / HBM_PEAK_BPS, 4),
+            "hbm_peak_note": "tap-weight bytes / device time / 8.0 TB/s; the packs fit the 256 MiB Infinity Cache, "
+                             "so this is an equivalent rate, not measured HBM traffic",
+            "host_restatement_ms_per_frame": round(cpu_ms, 2), "host_threads": torch.get_num_threads(),
+            "reference_cited": "BASELINE.md: CoST-GCN per-frame 204 ms (Kt=9), 1.351 s (Kt=69)"}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=2000)
@@ -291,6 +368,10 @@ def main():
                                     {"both": (True, False), "fused": (True,), "unfused": (False,)}[args.ln_route])), flush=True)
     if args.only in (None, "f1"):
         print(json.dumps(staging(P, dev)), flush=True)
+    if args.only == "co":
+        for kernel in (9, 69):
+            for dtype in ("fp32", "bf16"):
+                print(json.dumps(costgcn(P, dev, kernel, dtype)), flush=True)
 
 
 if __name__ == "__main__":
