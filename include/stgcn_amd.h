@@ -32,8 +32,9 @@ extern "C" {
  *   4: round 6 (stgcn_rt_frame + stgcn_rt_layer / stgcn_rt_frame_desc: the RT per-frame step in one launch;
  *      stgcn_gconv_wgrad_desc gained phase);
  *   5: round 6 (stgcn_bn_merge: one (count, mean, M2) entry per channel, the SyncBatchNorm exchange unit);
- *   6: stgcn_co_* + stgcn_co_layer: CoST-GCN per-frame inference (co_frame.hip). */
-#define STGCN_ABI_VERSION 6
+ *   6: stgcn_co_* + stgcn_co_layer: CoST-GCN per-frame inference (co_frame.hip);
+ *   7: stgcn_ms_* + stgcn_ms_layer / stgcn_ms_lin: MS-TCN stages, forward and backward (ms_stage.hip). */
+#define STGCN_ABI_VERSION 7
 
 /* Implicit-GEMM (Kt x 1) row convolution; see conv_rows.hip for the exact contract.
  * Replaces: nn.Conv2d tcn.2 (models/stgcn/stgcn.py:154-159), residual.0 (stgcn.py:165-170),
@@ -531,6 +532,74 @@ int stgcn_co_gcn(const stgcn_co_layer* d, void* stream);
 int stgcn_co_push(const stgcn_co_layer* d, void* stream);
 int stgcn_co_taps(const stgcn_co_layer* d, void* stream);
 int stgcn_co_finish(const stgcn_co_layer* d, void* stream);
+
+/* MS-TCN stage (models/mstcn/mstcn.py:68-116; ms_stage.hip): SingleStage = conv_in 1x1, num_layers
+ * DilatedResidualLayers (dilation 2^i), conv_out 1x1, forward and backward, batch 1.  Activations are fp32 rows
+ * [L][V][F] (row r = t*V + v); dtype (0 fp32 | 1 bf16) is the type MFMA operands are rounded to and the element type
+ * of the packed weights, of the saved hidden activation h and of its gradient g; accumulation is fp32 and the
+ * residual stream stays fp32.  Every hand-off is a kernel boundary, no atomics: results are run-to-run identical.
+ *
+ * One layer with dilation dil (kernel 3, padding dil: nn.Conv2d(F, F, (3,1), padding=(dil,0), dilation=(dil,1)),
+ * ReLU, nn.Conv2d(F, F, 1); dropout must be 0), R = L*V rows:
+ *   stgcn_ms_layer_fwd : h = ReLU(b1 + sum_k W1_k x[r + (k-1)*dil*V]) (rows outside [0, R) are the zero padding),
+ *                        y = x + b2 + W2 h; h is stored when h != NULL (training)
+ *   stgcn_ms_layer_bwd : g = (W2^T dy) . [h > 0];  dx = dy + sum_k W1_k^T g[r - (k-1)*dil*V] (skipped when
+ *                        dx == NULL);  grads = [dW1 (F,F,3) | db1 (F) | dW2 (F,F) | db2 (F)] summed in a fixed
+ *                        order from stgcn_ms_wgrad_blocks(R) per-workgroup partials (part: that many times
+ *                        4*F*F + 2*F floats)
+ * wp: stgcn_ms_pack_layer's image of W1 (F,F,3,1) and W2 (F,F,1,1): four MFMA fragment-order panels (W1 tap-major,
+ * W2, and both transposed), stgcn_ms_pack_elems(F) dtype elements; kernel != 3 is refused there.
+ * F in {16, 32, 48, 64}; R % V == 0; R * dil <= INT_MAX; anything else returns 1 before any launch. */
+typedef struct {
+  int R, V, F, dil, dtype, pad_;
+  const float* x;   /* [R][F] layer input */
+  const void* wp;   /* packed weights */
+  const float* b1;  /* [F] conv.0.bias */
+  const float* b2;  /* [F] conv.2.bias */
+  float* y;         /* [R][F] (forward) */
+  void* h;          /* [R][F] dtype elements: written by the forward (or NULL), read by the backward */
+  const float* dy;  /* [R][F] (backward) */
+  void* g;          /* [R][F] dtype elements, backward workspace */
+  float* dx;        /* [R][F] or NULL */
+  float* part;      /* backward workspace */
+  float* grads;     /* [4*F*F + 2*F] */
+} stgcn_ms_layer;
+long stgcn_ms_pack_elems(int F);
+int stgcn_ms_pack_layer(const float* w1, const float* w2, int F, int kernel, void* dst, int dtype, void* stream);
+int stgcn_ms_wgrad_blocks(int R);
+int stgcn_ms_layer_fwd(const stgcn_ms_layer* d, void* stream);
+int stgcn_ms_layer_bwd(const stgcn_ms_layer* d, void* stream);
+
+/* The two ends of a stage, fp32, plain FMA code (widths <= 64):
+ *   out[r][o] = b[o] + sum_i w[o][i] p[r][i],   p[r] = selector(mean_v in[r*pool + v]),   r < rows
+ * stgcn_ms_in_*  : conv_in with the model's `refine` selector fused in front (mstcn.py:63): mode 0 none | 1 log-softmax
+ *                  | 2 softmax over the I values of a row; pool == 1; O = filters.
+ * stgcn_ms_out_* : conv_out with the mean over the V = pool <= 32 joints fused in front (mstcn.py:58; the mean
+ *                  commutes with a 1x1 convolution); mode == 0; I = filters.
+ * The forward stores p when p != NULL (the backward reads it).  The backward writes grads = [dw (O,I) | db (O)],
+ * summed in a fixed order from stgcn_ms_lin_blocks(rows) partials (part: that many times O*I + O floats), and, when
+ * din != NULL, din[r*pool + v] = J^T (w^T d[r]) / pool (J: the selector's Jacobian at p). */
+typedef struct {
+  int rows, pool, I, O, mode, pad_;
+  const float* in;  /* [rows*pool][I] */
+  const float* w;   /* [O][I] */
+  const float* b;   /* [O] */
+  float* out;       /* [rows][O] */
+  float* p;         /* [rows][I] */
+  const float* d;   /* [rows][O] gradient of out (backward) */
+  float* din;       /* [rows*pool][I] or NULL */
+  float* part;
+  float* grads;     /* [O*I + O] */
+} stgcn_ms_lin;
+int stgcn_ms_lin_blocks(int rows);
+int stgcn_ms_in_fwd(const stgcn_ms_lin* d, void* stream);
+int stgcn_ms_in_bwd(const stgcn_ms_lin* d, void* stream);
+int stgcn_ms_out_fwd(const stgcn_ms_lin* d, void* stream);
+int stgcn_ms_out_bwd(const stgcn_ms_lin* d, void* stream);
+/* The model's `out` selector on [rows][C] fp32 rows, C <= 64 (mstcn.py:40-45): y = log-softmax (mode 1) | softmax
+ * (mode 2) of x, and dx from y and dy. */
+int stgcn_ms_prob_fwd(const float* x, int rows, int C, int mode, float* y, void* stream);
+int stgcn_ms_prob_bwd(const float* y, const float* dy, int rows, int C, int mode, float* dx, void* stream);
 
 /* Window staging (window.hip): the first activation of a batch of sliding windows
  * (WindowSegment, utils/segment_generator.py:132-145) computed from the padded capture without forming the

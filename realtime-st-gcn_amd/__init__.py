@@ -29,3 +29,10 @@ try:
     MODELS["co-st-gcn"] = CoStgcn
 except ImportError:  # pragma: no cover
     pass
+try:
+    from .mstcn import Model as MsTcn  # noqa: F401
+    from .msgcn import Model as MsGcn  # noqa: F401
+    MODELS["ms-tcn"] = MsTcn
+    MODELS["ms-gcn"] = MsGcn
+except ImportError:  # pragma: no cover
+    pass

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("STGCN_LIB") or os.path.join(_HERE, "lib", "libstgcn_amd.so")  # STGCN_LIB: A/B builds
 
 # the STGCN_ABI_VERSION of include/stgcn_amd.h these bindings mirror (test_cpu_host checks the two agree)
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 _ERR = {1: "bad shape/arguments", 2: "unsupported dtype", 3: "HIP launch error"}
 
@@ -109,6 +109,16 @@ class CoLayer(ctypes.Structure):  # stgcn_co_layer
                                         "partial", "y")]
 
 
+class MsLayer(ctypes.Structure):  # stgcn_ms_layer
+    _fields_ = [(n, c_int) for n in ("R", "V", "F", "dil", "dtype", "pad_")] + \
+               [(n, c_void_p) for n in ("x", "wp", "b1", "b2", "y", "h", "dy", "g", "dx", "part", "grads")]
+
+
+class MsLin(ctypes.Structure):  # stgcn_ms_lin
+    _fields_ = [(n, c_int) for n in ("rows", "pool", "I", "O", "mode", "pad_")] + \
+               [(n, c_void_p) for n in ("in_", "w", "b", "out", "p", "d", "din", "part", "grads")]
+
+
 # name -> (restype, argtypes)
 _SIGS = {
     "stgcn_abi_version": (c_int, []),
@@ -197,6 +207,18 @@ _SIGS = {
     "stgcn_co_push": (c_int, [ctypes.POINTER(CoLayer), c_void_p]),
     "stgcn_co_taps": (c_int, [ctypes.POINTER(CoLayer), c_void_p]),
     "stgcn_co_finish": (c_int, [ctypes.POINTER(CoLayer), c_void_p]),
+    "stgcn_ms_pack_elems": (c_long, [c_int]),
+    "stgcn_ms_pack_layer": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "stgcn_ms_wgrad_blocks": (c_int, [c_int]),
+    "stgcn_ms_layer_fwd": (c_int, [ctypes.POINTER(MsLayer), c_void_p]),
+    "stgcn_ms_layer_bwd": (c_int, [ctypes.POINTER(MsLayer), c_void_p]),
+    "stgcn_ms_lin_blocks": (c_int, [c_int]),
+    "stgcn_ms_in_fwd": (c_int, [ctypes.POINTER(MsLin), c_void_p]),
+    "stgcn_ms_in_bwd": (c_int, [ctypes.POINTER(MsLin), c_void_p]),
+    "stgcn_ms_out_fwd": (c_int, [ctypes.POINTER(MsLin), c_void_p]),
+    "stgcn_ms_out_bwd": (c_int, [ctypes.POINTER(MsLin), c_void_p]),
+    "stgcn_ms_prob_fwd": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "stgcn_ms_prob_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "stgcn_window_stat_blocks": (c_int, [c_int, c_int]),
     "stgcn_window_stats": (c_int, [c_void_p] + [c_int] * 7 + [c_float, c_void_p, c_void_p]),
     "stgcn_window_expand": (c_int, [c_void_p] + [c_int] * 7 + [c_void_p] * 5 + [c_int, c_void_p, c_int, c_int,

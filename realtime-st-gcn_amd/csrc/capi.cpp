@@ -117,6 +117,15 @@ int co_gcn_launch(const stgcn_co_layer& d, hipStream_t s);
 int co_push_launch(const stgcn_co_layer& d, hipStream_t s);
 int co_taps_launch(const stgcn_co_layer& d, hipStream_t s);
 int co_finish_launch(const stgcn_co_layer& d, hipStream_t s);
+long ms_pack_elems(int F);
+int ms_pack_launch(const float* w1, const float* w2, int F, int kernel, void* dst, int dtype, hipStream_t s);
+int ms_wgrad_blocks(int R);
+int ms_layer_fwd_launch(const stgcn_ms_layer& d, hipStream_t s);
+int ms_layer_bwd_launch(const stgcn_ms_layer& d, hipStream_t s);
+int ms_lin_blocks(int rows);
+int ms_lin_fwd_launch(const stgcn_ms_lin& d, int which, hipStream_t s);
+int ms_lin_bwd_launch(const stgcn_ms_lin& d, int which, hipStream_t s);
+int ms_prob_launch(const float* y, const float* dy, float* out, int rows, int C, int mode, hipStream_t s);
 int window_stat_blocks_launch(int nw, int W);
 int window_stats_launch(const float* x, int Cin, int Lp, int V, int W, int n0, int nw, int mode, float eps, float* out,
                         hipStream_t s);
@@ -475,6 +484,37 @@ CO_ENTRY(stgcn_co_push, co_push_launch)
 CO_ENTRY(stgcn_co_taps, co_taps_launch)
 CO_ENTRY(stgcn_co_finish, co_finish_launch)
 #undef CO_ENTRY
+
+long stgcn_ms_pack_elems(int F) { return ms_pack_elems(F); }
+int stgcn_ms_pack_layer(const float* w1, const float* w2, int F, int kernel, void* dst, int dtype, void* stream) {
+  return ms_pack_launch(w1, w2, F, kernel, dst, dtype, STREAM(stream));
+}
+int stgcn_ms_wgrad_blocks(int R) { return ms_wgrad_blocks(R); }
+int stgcn_ms_layer_fwd(const stgcn_ms_layer* d, void* stream) {
+  return d ? ms_layer_fwd_launch(*d, STREAM(stream)) : STGCN_EBADSHAPE;
+}
+int stgcn_ms_layer_bwd(const stgcn_ms_layer* d, void* stream) {
+  return d ? ms_layer_bwd_launch(*d, STREAM(stream)) : STGCN_EBADSHAPE;
+}
+int stgcn_ms_lin_blocks(int rows) { return ms_lin_blocks(rows); }
+int stgcn_ms_in_fwd(const stgcn_ms_lin* d, void* stream) {
+  return d ? ms_lin_fwd_launch(*d, 0, STREAM(stream)) : STGCN_EBADSHAPE;
+}
+int stgcn_ms_in_bwd(const stgcn_ms_lin* d, void* stream) {
+  return d ? ms_lin_bwd_launch(*d, 0, STREAM(stream)) : STGCN_EBADSHAPE;
+}
+int stgcn_ms_out_fwd(const stgcn_ms_lin* d, void* stream) {
+  return d ? ms_lin_fwd_launch(*d, 1, STREAM(stream)) : STGCN_EBADSHAPE;
+}
+int stgcn_ms_out_bwd(const stgcn_ms_lin* d, void* stream) {
+  return d ? ms_lin_bwd_launch(*d, 1, STREAM(stream)) : STGCN_EBADSHAPE;
+}
+int stgcn_ms_prob_fwd(const float* x, int rows, int C, int mode, float* y, void* stream) {
+  return ms_prob_launch(x, nullptr, y, rows, C, mode, STREAM(stream));
+}
+int stgcn_ms_prob_bwd(const float* y, const float* dy, int rows, int C, int mode, float* dx, void* stream) {
+  return dy ? ms_prob_launch(y, dy, dx, rows, C, mode, STREAM(stream)) : STGCN_EBADSHAPE;
+}
 
 int stgcn_window_stat_blocks(int nw, int W) { return window_stat_blocks_launch(nw, W); }
 int stgcn_window_stats(const float* x, int Cin, int Lp, int V, int W, int n0, int nw, int mode, float eps, float* out,

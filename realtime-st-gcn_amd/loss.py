@@ -103,6 +103,18 @@ class Loss:
         return SegLossFunction.apply(predictions, ground_truth, self.weight, first, self.mode, prev, den, pairs)
 
 
+class LossMultiStage(Loss):
+    """utils/loss.py:44-54: the loss of every stage of a (stages, 1, C, L) prediction (ms-tcn / ms-gcn), summed."""
+
+    def __call__(self, i, predictions, ground_truth, shard=None):
+        ce_tot = mse_tot = 0
+        for k in range(predictions.size(0)):
+            ce, mse = super().__call__(i, predictions[k], ground_truth, shard)
+            ce_tot = ce_tot + ce
+            mse_tot = mse_tot + mse
+        return ce_tot, mse_tot
+
+
 class Statistics:
     """utils/statistics.py:4-16: top-1 / top-5 hits of the series (frame 0 dropped for i > 0)."""
 
@@ -115,3 +127,10 @@ class Statistics:
         top1_predicted = t5[:, 0, :]
         h = out[2:4].tolist()
         return top1_predicted, t5, int(h[0]), int(h[1]), ground_truth.numel()
+
+
+class StatisticsMultiStage(Statistics):
+    """utils/statistics.py:19-21: the statistics of the last stage of a (stages, 1, C, L) prediction."""
+
+    def __call__(self, i, predictions, ground_truth):
+        return super().__call__(i, predictions[-1], ground_truth)

@@ -1078,6 +1078,105 @@ def co_layer_frame(desc):
     L.check(lib.stgcn_co_finish(d, s), "co_finish")
 
 
+# ------------------------------------------------------------------------------ MS-TCN stage (ms_stage.hip)
+MS_MODES = {"logits": 0, "logsoftmax": 1, "softmax": 2}  # the `refine` / `output_type` selectors
+
+
+def _rows32(t):
+    """fp32 contiguous [rows][C] on the device."""
+    L.require_device(t)
+    return _f32c(t)
+
+
+def ms_pack_layer(w1, w2, dtype):
+    """conv.0 (F, F, 3, 1) and conv.2 (F, F, 1, 1) weights -> the layer kernels' four MFMA panels in ``dtype``."""
+    L.require_device(w1)
+    F, kernel = w1.shape[0], w1.shape[2]
+    n = L.lib().stgcn_ms_pack_elems(F)
+    if n < 0 or kernel != 3:
+        raise RuntimeError(f"stgcn_amd: ms_pack_layer: unsupported layer (filters {F}, kernel {kernel}): "
+                           "filters in {16, 32, 48, 64} and kernel 3")
+    out = torch.empty(n, dtype=dtype, device=w1.device)
+    L.check(L.lib().stgcn_ms_pack_layer(_f32c(w1.detach()).data_ptr(), _f32c(w2.detach()).data_ptr(), F, kernel,
+                                        out.data_ptr(), L.dtype_code(dtype), L.stream()), "ms_pack_layer")
+    return out
+
+
+def ms_layer_fwd(x, wp, b1, b2, V, dil, dtype, save):
+    """One dilated residual layer on fp32 rows x [R][F] -> (y [R][F] fp32, h [R][F] ``dtype`` or None)."""
+    R, F = x.shape
+    y = torch.empty_like(x)
+    h = torch.empty((R, F), dtype=dtype, device=x.device) if save else None
+    d = L.MsLayer(R=R, V=V, F=F, dil=dil, dtype=L.dtype_code(dtype), x=x.data_ptr(), wp=wp.data_ptr(),
+                  b1=_f32c(b1.detach()).data_ptr(), b2=_f32c(b2.detach()).data_ptr(), y=y.data_ptr(), h=L.ptr(h))
+    L.check(L.lib().stgcn_ms_layer_fwd(ctypes.byref(d), L.stream()), "ms_layer_fwd")
+    return y, h
+
+
+def ms_layer_bwd(x, wp, h, dy, V, dil, dtype, need_dx=True):
+    """-> (dx [R][F] fp32 or None, grads [4 F^2 + 2 F] = dW1 (F,F,3) | db1 | dW2 (F,F) | db2)."""
+    R, F = x.shape
+    dev = x.device
+    E = 4 * F * F + 2 * F
+    g = torch.empty((R, F), dtype=dtype, device=dev)
+    dx = torch.empty_like(x) if need_dx else None
+    part = torch.empty(L.lib().stgcn_ms_wgrad_blocks(R) * E, dtype=torch.float32, device=dev)
+    grads = torch.empty(E, dtype=torch.float32, device=dev)
+    d = L.MsLayer(R=R, V=V, F=F, dil=dil, dtype=L.dtype_code(dtype), x=x.data_ptr(), wp=wp.data_ptr(),
+                  h=h.data_ptr(), dy=dy.data_ptr(), g=g.data_ptr(), dx=L.ptr(dx), part=part.data_ptr(),
+                  grads=grads.data_ptr())
+    L.check(L.lib().stgcn_ms_layer_bwd(ctypes.byref(d), L.stream()), "ms_layer_bwd")
+    return dx, grads
+
+
+def _ms_lin(which):
+    lib = L.lib()
+    return (lib.stgcn_ms_in_fwd, lib.stgcn_ms_in_bwd) if which == "in" else (lib.stgcn_ms_out_fwd, lib.stgcn_ms_out_bwd)
+
+
+def ms_lin_fwd(which, x, w, b, pool, mode, save):
+    """``which`` "in": conv_in with the selector ``mode`` fused in front; "out": conv_out after the mean over
+    ``pool`` joints.  x fp32 [rows * pool][I] -> (out [rows][O], p [rows][I] (the convolution's input) or None)."""
+    I, O = x.shape[1], w.shape[0]
+    rows = x.shape[0] // pool
+    out = torch.empty((rows, O), dtype=torch.float32, device=x.device)
+    p = torch.empty((rows, I), dtype=torch.float32, device=x.device) if save else None
+    d = L.MsLin(rows=rows, pool=pool, I=I, O=O, mode=mode, in_=x.data_ptr(), w=_f32c(w.detach()).data_ptr(),
+                b=_f32c(b.detach()).data_ptr(), out=out.data_ptr(), p=L.ptr(p))
+    L.check(_ms_lin(which)[0](ctypes.byref(d), L.stream()), f"ms_{which}_fwd")
+    return out, p
+
+
+def ms_lin_bwd(which, dout, p, w, pool, mode, need_din):
+    """-> (din [rows * pool][I] or None, grads [O I + O] = dw (O, I) | db)."""
+    rows, O = dout.shape
+    I = p.shape[1]
+    dev = dout.device
+    E = O * I + O
+    din = torch.empty((rows * pool, I), dtype=torch.float32, device=dev) if need_din else None
+    part = torch.empty(L.lib().stgcn_ms_lin_blocks(rows) * E, dtype=torch.float32, device=dev)
+    grads = torch.empty(E, dtype=torch.float32, device=dev)
+    d = L.MsLin(rows=rows, pool=pool, I=I, O=O, mode=mode, w=_f32c(w.detach()).data_ptr(), p=p.data_ptr(),
+                d=dout.data_ptr(), din=L.ptr(din), part=part.data_ptr(), grads=grads.data_ptr())
+    L.check(_ms_lin(which)[1](ctypes.byref(d), L.stream()), f"ms_{which}_bwd")
+    return din, grads
+
+
+def ms_prob_fwd(x, mode):
+    """log-softmax (mode 1) | softmax (2) over the classes of fp32 rows [rows][C]."""
+    y = torch.empty_like(x)
+    L.check(L.lib().stgcn_ms_prob_fwd(x.data_ptr(), x.shape[0], x.shape[1], mode, y.data_ptr(), L.stream()),
+            "ms_prob_fwd")
+    return y
+
+
+def ms_prob_bwd(y, dy, mode):
+    dx = torch.empty_like(y)
+    L.check(L.lib().stgcn_ms_prob_bwd(y.data_ptr(), dy.data_ptr(), y.shape[0], y.shape[1], mode, dx.data_ptr(),
+                                      L.stream()), "ms_prob_bwd")
+    return dx
+
+
 # ------------------------------------------------------------------------------ window staging (window.hip)
 def _capture(x):
     """(1, Cin, Lp, V) padded capture -> contiguous fp32 [Cin][Lp][V] on the device."""

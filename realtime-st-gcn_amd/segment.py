@@ -116,6 +116,26 @@ class WindowSegment(Segment):
         return predictions.permute(2, 1, 0)  # (N', C', 1) -> (1, C', N')
 
 
+class WindowSegmentMultiStage(WindowSegment):
+    """segment_generator.py:157-160 (ms-gcn): the model already returns the (stages, 1, C, L) series."""
+
+    def mask_segment(self, L, P_start, P_end, predictions):
+        return predictions
+
+
+class WindowSegmentOneToOneMultiStage(Segment):
+    """segment_generator.py:163-173 (ms-tcn): the whole capture is one batch, unpadded."""
+
+    def pad_sequence(self, L):
+        return 0, 0
+
+    def get_segment(self, captures):
+        return captures
+
+    def mask_segment(self, L, P_start, P_end, predictions):
+        return predictions
+
+
 class BufferSegment(Segment):
     """segment_generator.py:18-106: chunks of ``segment`` frames overlapping by G-1 (G = ``kernel``), or, with
     ``segment`` None, ``world_size`` equal chunks."""

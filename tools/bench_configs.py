@@ -17,7 +17,13 @@ co:       CoST-GCN continual inference (config/pku-mmd/ln/costgcn_local.json wid
           the tap-weight bytes one frame reads and the HBM-peak fraction they imply, and the plain-PyTorch
           restatement (tests/costgcn_ref.py) timed on the host.  Only with --only co.
 
-    python tools/bench_configs.py [--frames 2000] [--steps 10] [--only 3|5|ln|f1|co]
+ms:       MS-TCN refinement stage (F = 64, 10 layers, 52 classes, L = 2000; ms_stage.hip) forward and backward, fp32
+          and bf16, with per-layer kernel times against the bytes a layer moves, and one ms-gcn training step
+          (config/pku-mmd/as_is/msgcn_vsc.json: BatchNorm ST-GCN generator over 2000 windows of 50 frames + 3
+          refinement stages; LossMultiStage, backward, Adam).  The plain-PyTorch restatement of the stage
+          (tests/mstcn_ref.py) is timed on the host beside it.  Only with --only ms.
+
+    python tools/bench_configs.py [--frames 2000] [--steps 10] [--only 3|5|ln|f1|co|ms]
 Prints one JSON line per config.
 """
 import argparse
@@ -348,6 +354,117 @@ def costgcn(P, dev, kernel, dtype, frames=256, cpu_frames=3):
             "reference_cited": "BASELINE.md: CoST-GCN per-frame 204 ms (Kt=9), 1.351 s (Kt=69)"}
 
 
+MS_TCN = {"latency": False, "importance": True, "stages": 3, "layers": [10, 10, 10], "kernel": [3, 3, 3],
+          "filters": [64, 64, 64], "dropout": [0, 0, 0]}
+MSGCN_ARCH = {"strategy": "spatial", "receptive_field": 50, "segment": 2000, "in_feat": 3, "stages": 4,
+              "refine": "softmax", "output_type": "logits", "normalization": "BatchNorm", "num_classes": 52,
+              "st-gcn": dict(LAYERS, latency=False, importance=True, in_feat=3, stages=1), "ms-tcn": MS_TCN}
+
+
+def _dev_ms(fn, reps, warm=3):
+    for _ in range(warm):
+        fn()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+def ms_stage(P, dev, dtype, L=2000, F=64, C=52, nl=10, reps=20):
+    """One refinement stage on a (1, C, L, 1) series: forward, forward + backward, and each layer kernel alone."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import mstcn_ref as R
+    K = P.native
+    dt = torch.bfloat16 if dtype == "bf16" else torch.float32
+    torch.manual_seed(0)
+    st = P.mstcn.SingleStage(in_channels=C, out_channels=C, num_filters=F, num_layers=nl, kernel=3, dropout=0.0)
+    sd = {k: v.clone() for k, v in st.state_dict().items()}
+    st = st.to(dev).train()
+    st.compute_dtype = dt
+    x = torch.randn(L, C, device=dev, requires_grad=True)
+    g = torch.randn(L, C, device=dev)
+
+    def fwd():
+        with torch.no_grad():
+            st.run_rows(x, 1, 1, 2)
+
+    def fwd_bwd():
+        st.zero_grad(set_to_none=True)
+        x.grad = None
+        (st.run_rows(x, 1, 1, 2) * g).sum().backward()
+
+    es = 2 if dtype == "bf16" else 4
+    a = torch.randn(L, F, device=dev)
+    layers = []
+    for j, layer in enumerate(st.layers):
+        wp = K.ms_pack_layer(layer.conv[0].weight, layer.conv[2].weight, dt)
+        b1, b2 = layer.conv[0].bias, layer.conv[2].bias
+        _, h = K.ms_layer_fwd(a, wp, b1, b2, 1, 2 ** j, dt, True)
+        t_f = _dev_ms(lambda: K.ms_layer_fwd(a, wp, b1, b2, 1, 2 ** j, dt, True), 50)
+        t_b = _dev_ms(lambda: K.ms_layer_bwd(a, wp, h, a, 1, 2 ** j, dt), 50)
+        # algorithmic bytes: forward reads x and the W1 | W2 panels, writes y and h; backward (4 launches) reads dy
+        # (three times), h (twice), x, g (twice), the transposed panels and the partials, writes g, dx, partials, grads
+        by_f = L * F * (8 + es) + 4 * F * F * es
+        by_b = L * F * (20 + 5 * es) + 4 * F * F * es + 2 * (4 * F * F + 2 * F) * 4 * P._lib.lib().stgcn_ms_wgrad_blocks(L)
+        layers.append({"dilation": 2 ** j, "fwd_us": round(1e3 * t_f, 2), "bwd_us": round(1e3 * t_b, 2),
+                       "fwd_bytes": by_f, "bwd_bytes": by_b, "fwd_GBps": round(by_f / (t_f * 1e-3) / 1e9, 1),
+                       "bwd_GBps": round(by_b / (t_b * 1e-3) / 1e9, 1)})
+    t_fwd, t_step = _dev_ms(fwd, reps), _dev_ms(fwd_bwd, reps)
+    xc, gc = x.detach().cpu().t().reshape(1, C, L, 1), g.cpu().t().reshape(1, C, L, 1)
+
+    def host():
+        R.grads_of(lambda a_, s_: R.single_stage(torch.softmax(a_, 1), s_, round_bf16=dtype == "bf16"), xc, sd, gc,
+                   input_grad=True)
+    host()
+    t0 = time.perf_counter()
+    for _ in range(3):
+        host()
+    cpu_ms = 1e3 * (time.perf_counter() - t0) / 3
+    return {"config": f"ms-tcn refinement stage: softmax + conv_in {C}->{F}, {nl} dilated residual layers, conv_out "
+                      f"{F}->{C}, series (1,{C},{L},1)", "metric": "device time per call (HIP events, eager launches)",
+            "unit": "ms", "dtype": dtype, "fwd_ms": round(t_fwd, 4), "fwd_bwd_ms": round(t_step, 4),
+            "launches_fwd": 2 + 2 * nl, "launches_bwd": 4 + 4 * nl, "layers": layers,
+            "host_restatement_fwd_bwd_ms": round(cpu_ms, 2), "host_threads": torch.get_num_threads()}
+
+
+def msgcn_step(P, dev, dtype, steps, L=2000):
+    """One ms-gcn training step on one trial of L frames (one segment of L windows)."""
+    arch = dict(MSGCN_ARCH, graph=P.PKU_MMD)
+    torch.manual_seed(0)
+    m = P.MODELS["ms-gcn"](rank=None, **arch).to(dev).train().set_compute_dtype(dtype)
+    W = arch["receptive_field"]
+    capture = torch.randn(1, 3, L + W - 1, 25, device=dev)
+    labels = torch.randint(0, 52, (1, L), device=dev)
+    batch = P.segment.WindowBatch(capture, 0, L, W)
+    loss_fn = P.loss.LossMultiStage(dev, torch.ones(52))
+    opt = P.optim.Adam(m.parameters(), lr=5e-4)
+
+    def step():
+        opt.zero_grad(set_to_none=True)
+        ce, mse = loss_fn(0, m(batch), labels)
+        (ce + mse).backward()
+        opt.step()
+
+    def refine_only():
+        with torch.no_grad():
+            y = torch.zeros(L, 52, device=dev)
+        y.requires_grad_(True)
+        out = P.mstcn.refine_and_stack(y, m.refinement_stages, m.refine_mode, m.out_mode)
+        ce, mse = loss_fn(0, out, labels)
+        (ce + mse).backward()
+
+    t_step = _dev_ms(step, steps, warm=2)
+    t_ref = _dev_ms(refine_only, steps, warm=2)
+    return {"config": f"ms-gcn training step (as_is/msgcn_vsc.json: BatchNorm st-gcn generator, {L} windows of {W} "
+                      "frames, 3 refinement stages of 10 layers, F=64, 52 classes), LossMultiStage + Adam",
+            "metric": "device time per step (HIP events)", "unit": "ms", "dtype": dtype, "steps": steps,
+            "step_ms": round(t_step, 3), "refinement_and_loss_fwd_bwd_ms": round(t_ref, 3),
+            "refinement_share": round(t_ref / t_step, 4)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=2000)
@@ -368,6 +485,11 @@ def main():
                                     {"both": (True, False), "fused": (True,), "unfused": (False,)}[args.ln_route])), flush=True)
     if args.only in (None, "f1"):
         print(json.dumps(staging(P, dev)), flush=True)
+    if args.only == "ms":
+        for dtype in ("fp32", "bf16"):
+            print(json.dumps(ms_stage(P, dev, dtype)), flush=True)
+        for dtype in ("fp32", "bf16"):
+            print(json.dumps(msgcn_step(P, dev, dtype, min(args.steps, 5))), flush=True)
     if args.only == "co":
         for kernel in (9, 69):
             for dtype in ("fp32", "bf16"):
