@@ -19,6 +19,7 @@
 // from the stored head, co_finish stores it.  Entry of age j lives in slot (head' + j) % fifo.
 // No floating-point atomics anywhere: a stream replays bit-identically.
 #include "common.h"
+#include "frame_ops.h"
 #include "../../include/stgcn_amd.h"
 
 namespace {
@@ -31,33 +32,6 @@ constexpr int PMAX = 3;
 constexpr int KTMAX = 69;
 constexpr int FNT = 1024;  // co_push / co_finish block
 constexpr int U4 = 2;      // float4 units per thread there: V * C <= 8192
-
-DEV float block_sum(float v, float* red) {  // fixed order; every thread gets the total
-  v = wave_sum(v);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) red[w] = v;
-  __syncthreads();
-  float t = 0.f;
-  for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t += red[i];
-  return t;
-}
-
-DEV float dot8(const float* __restrict__ w, const float* x, int K4, int kk) {
-  const float4* w4 = reinterpret_cast<const float4*>(w);
-  const float4* x4 = reinterpret_cast<const float4*>(x);
-  float s = 0.f;
-  for (int k = kk; k < K4; k += 8) {
-    const float4 a = w4[k], b = x4[k];
-    s = fmaf(a.x, b.x, s);
-    s = fmaf(a.y, b.y, s);
-    s = fmaf(a.z, b.z, s);
-    s = fmaf(a.w, b.w, s);
-  }
-#pragma unroll
-  for (int m = 1; m < 8; m <<= 1) s += __shfl_xor(s, m);
-  return s;
-}
 
 // y_p[u][co] = W_p[co] . x[u] for the block's CB channels, then z[v][co] = bias2d[v][co] + sum_{p,u} A[p][u][v] y_p[u][co];
 // r[v][co] = br[co] + Wr[co] . x[v]
@@ -99,12 +73,6 @@ __global__ __launch_bounds__(NT) void co_gcn_kernel(const float* __restrict__ x,
       if (Wr) r_out[e] = r + (br ? br[co] : 0.f);
     }
   }
-}
-
-DEV float sum4(float4 v) { return (v.x + v.y) + (v.z + v.w); }
-DEV float sq4(float4 v, float m) {
-  const float a = v.x - m, b = v.y - m, c = v.z - m, d = v.w - m;
-  return fmaf(a, a, fmaf(b, b, fmaf(c, c, d * d)));
 }
 
 // two-pass LayerNorm statistics (mean, 1 / sqrt(unbiased var + eps)) of the n = 4 * n4 values the block holds in

@@ -14,6 +14,10 @@ typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x8 __attribute__((ext_vector_type(8)));
+// bf16 bit patterns as the transposed LDS reads return them (lds_ops.h)
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+typedef short s16x8 __attribute__((ext_vector_type(8)));
+typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
 #define DEV __device__ __forceinline__
 
@@ -77,6 +81,47 @@ DEV uint4 pack16(const float* f, float*) {
   return __builtin_bit_cast(uint4, v);
 }
 
+// MFMA fragment from LDS rows that hold consecutive k: bf16 = the 16 B at p0; fp32 = the 16 B at p0 (elements
+// 0..3) and at p1 (4..7)
+template <typename T>
+DEV typename Tr<T>::frag frag2(const char* p0, const char* p1) {
+  if constexpr (sizeof(T) == 2) {
+    (void)p1;
+    return __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(p0));
+  } else {
+    const f32x4 a = __builtin_bit_cast(f32x4, *reinterpret_cast<const uint4*>(p0));
+    const f32x4 b = __builtin_bit_cast(f32x4, *reinterpret_cast<const uint4*>(p1));
+    f32x8 f;
+    f[0] = a[0]; f[1] = a[1]; f[2] = a[2]; f[3] = a[3];
+    f[4] = b[0]; f[5] = b[1]; f[6] = b[2]; f[7] = b[3];
+    return f;
+  }
+}
+
+// LDS pointer -> its 32-bit LDS offset (what M0 and the asm DMA of lds_ops.h take)
+DEV unsigned lds_u32(const void* p) { return (unsigned)(size_t)(const __attribute__((address_space(3))) char*)p; }
+
+// Workgroup barrier for LDS hand-offs only: waits for this wave's LDS ops (lgkmcnt) but NOT for its outstanding
+// global loads, DMA and stores -- __syncthreads() would drain vmcnt, i.e. every prefetch ring, at each hand-off.
+// The "memory" clobber keeps the compiler from moving memory ops across it.
+DEV void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// s_waitcnt vmcnt(n) for a wave-uniform run-time n (clamped to 63, the counter's range: waiting for fewer
+// outstanding operations is always safe)
+template <int N>
+DEV void wait_vm_upto(int n) {
+  if constexpr (N < 63) {
+    if (n <= N) {
+      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+      return;
+    }
+    wait_vm_upto<N + 1>(n);
+  } else {
+    asm volatile("s_waitcnt vmcnt(63)" ::: "memory");
+  }
+}
+DEV void wait_vm(int n) { wait_vm_upto<0>(n < 0 ? 0 : n); }
+
 // C/D map of the 32x32 MFMAs (dtype independent on gfx950): col = lane&31,
 // row = (r&3) + 8*(r>>2) + 4*(lane>>5), r = accumulator register 0..15.
 DEV int acc_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
@@ -101,6 +146,17 @@ DEV float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
   return v;
+}
+// fixed-order block sum through red[blockDim.x / 64]: every thread gets the total
+DEV float block_sum(float v, float* red) {
+  v = wave_sum(v);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  __syncthreads();
+  if (lane == 0) red[w] = v;
+  __syncthreads();
+  float t = 0.f;
+  for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t += red[i];
+  return t;
 }
 
 // status codes of the C-ABI (include/stgcn_amd.h)

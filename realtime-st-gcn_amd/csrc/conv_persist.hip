@@ -20,6 +20,7 @@
 //   * tap dt reads frame slot (f0 + fl + q(dt)) mod RS, q = dt (fwd) or 8 - dt (transposed = data
 //     gradient); a tile that starts a new sample is staged in an extra synchronous phase.
 #include "common.h"
+#include "lds_ops.h"
 #include "../../include/stgcn_amd.h"
 #include <stdlib.h>
 
@@ -38,12 +39,6 @@ constexpr int LDS_MAX = 160 * 1024;
 constexpr int RA = ROWS * 8 / GT;      // steady-state units per thread of a group: F*V <= 128 rows -> 4
 
 DEV int swz(int row) { return (row >> 1) & 7; }  // weight rows: 2 rows per 256-B bank row
-
-DEV void glds16(const void* src, char* lds_base) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)lds_base, 16, 0, 0);
-#endif
-}
 
 struct PGeom {
   int F;        // frames per tile

@@ -25,6 +25,7 @@
 // written after them, one barrier per chunk.  blockIdx is remapped so consecutive tiles (which
 // share halo frames and, for several column tiles, the whole A halo) land on the same XCD.
 #include "common.h"
+#include "lds_ops.h"
 #include "../../include/stgcn_amd.h"
 #include <stdlib.h>
 
@@ -38,28 +39,6 @@ struct TL {
   static constexpr int RS = RB + 16;                     // A row stride (padded)
   static DEV int swz(int row) { return (row / RPB) & (UPR - 1); }
 };
-
-// 16-byte LDS-DMA: lane l writes lds_base + 16*l (device-only builtin)
-DEV void glds16(const void* src, char* lds_base) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)lds_base, 16, 0, 0);
-#endif
-}
-
-template <typename T>
-DEV typename Tr<T>::frag frag2(const char* p0, const char* p1) {
-  if constexpr (sizeof(T) == 2) {
-    (void)p1;
-    return __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(p0));
-  } else {
-    const f32x4 a = __builtin_bit_cast(f32x4, *reinterpret_cast<const uint4*>(p0));
-    const f32x4 b = __builtin_bit_cast(f32x4, *reinterpret_cast<const uint4*>(p1));
-    f32x8 f;
-    f[0] = a[0]; f[1] = a[1]; f[2] = a[2]; f[3] = a[3];
-    f[4] = b[0]; f[5] = b[1]; f[6] = b[2]; f[7] = b[3];
-    return f;
-  }
-}
 
 struct TileGeom {
   int F;           // output frames per tile (framed) ; 0 = flat mode

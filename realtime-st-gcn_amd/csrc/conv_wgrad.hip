@@ -12,7 +12,7 @@
 // Grid: x = m-range, y = tap dt, z = (co tile, ci tile); block tile 64(co) x 64(ci), 4 waves
 // each owning a 32x32 quadrant; K walked in 32-row steps, double-buffered.
 #include "common.h"
-
+#include "lds_ops.h"
 #include "../../include/stgcn_amd.h"
 typedef stgcn_wgrad_desc WgradArgs;
 
@@ -20,9 +20,6 @@ namespace {
 
 constexpr int MK = 32;   // rows per K step
 constexpr int TC = 64;   // output tile (co and ci)
-
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
 template <typename T>
 DEV typename Tr<T>::frag tr_frag(const char* panel, int ks, int lane) {
@@ -32,14 +29,7 @@ DEV typename Tr<T>::frag tr_frag(const char* panel, int ks, int lane) {
     const int q = i >> 2, p = i & 3, h = g >> 1;
     const int row = ks * 16 + 8 * h + q;
     const int col = 16 * (g & 1) + 4 * p;
-    const char* a0 = panel + row * 64 + col * 2;
-    s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(a0));
-    s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(a0 + 4 * 64));
-    typedef short s16x8 __attribute__((ext_vector_type(8)));
-    s16x8 v;
-    v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-    v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-    return __builtin_bit_cast(bf16x8, v);
+    return trpair(panel + row * 64 + col * 2);
   } else {
     const float* pf = reinterpret_cast<const float*>(panel);
     const int c = lane & 31, h = lane >> 5;

@@ -27,10 +27,10 @@
 //   * epilogue per tile: + bias, bf16 store, BatchNorm Welford partials per (tile, channel) (the
 //     float4 (count, mean, M2) layout bn_finalize merges; row-tile index = n * tiles_n + tile).
 #include "common.h"
+#include "lds_ops.h"
 #include "pack.h"
 #include "../../include/stgcn_amd.h"
 #include <stdlib.h>
-#include <utility>
 
 namespace {
 
@@ -49,19 +49,6 @@ constexpr int abytes_for(int kg) {
   return halo > 128 * CSO ? halo : 128 * CSO;
 }
 constexpr int LDS_MAX = 160 * 1024;
-
-// compile-time loop: f.template operator()<I>() for I = 0..N-1 (guaranteed unrolled; register arrays
-// indexed by I never fall back to scratch)
-template <int N, typename F>
-DEV void static_for(F&& f) {
-  [&]<int... I>(std::integer_sequence<int, I...>) { (f.template operator()<I>(), ...); }(
-      std::make_integer_sequence<int, N>{});
-}
-
-// Workgroup barrier for LDS hand-offs only: waits for this wave's LDS ops (lgkmcnt) but NOT for its
-// outstanding global loads — __syncthreads() would drain the B-fragment prefetch ring (vmcnt(0)) at
-// every 64-channel item.  The "memory" clobber keeps the compiler from moving memory ops across it.
-DEV void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 struct WGeom {
   int F;        // output frames per tile

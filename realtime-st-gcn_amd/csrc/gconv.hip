@@ -23,9 +23,9 @@
 // tile); A rows staged through registers into padded LDS rows, B (packed Weff) by LDS-DMA with the
 // XOR swizzle on the source, fragment double-buffering, BN partial statistics in the epilogue.
 #include "common.h"
+#include "lds_ops.h"
 #include "pack.h"
 #include <stdlib.h>
-#include <utility>
 #include "../../include/stgcn_amd.h"
 
 #ifndef GCONV_NSTG_N
@@ -57,21 +57,6 @@ struct GL {
   static DEV int swz(int row) { return (row / RPB) & (UPR - 1); }
 };
 
-DEV void glds16(const void* src, char* lds_base) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)lds_base, 16, 0, 0);
-#endif
-}
-
-// global -> LDS DMA of 16 B per lane at a wave-uniform LDS offset, through asm so the compiler inserts no
-// alias-driven vmcnt drains (the DMA K loop counts its own); m0 saved / restored
-DEV void gdma16(const void* src, unsigned lds_off) {
-  unsigned saved;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t"
-               "s_mov_b32 m0, %0"
-               : "=&s"(saved) : "v"(src), "s"(__builtin_amdgcn_readfirstlane(lds_off)) : "memory");
-}
-DEV unsigned glds_off(const void* p) { return (unsigned)(size_t)(const __attribute__((address_space(3))) char*)p; }
 // s_waitcnt vmcnt(n) for the counts the DMA K loop uses (n = steps in flight x instructions per step)
 DEV void gwait_vm(int n) {
   switch (n) {
@@ -82,21 +67,6 @@ DEV void gwait_vm(int n) {
     case 9: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
     case 12: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
     default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-  }
-}
-
-template <typename T>
-DEV typename Tr<T>::frag frag2(const char* p0, const char* p1) {
-  if constexpr (sizeof(T) == 2) {
-    (void)p1;
-    return __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(p0));
-  } else {
-    const f32x4 a = __builtin_bit_cast(f32x4, *reinterpret_cast<const uint4*>(p0));
-    const f32x4 b = __builtin_bit_cast(f32x4, *reinterpret_cast<const uint4*>(p1));
-    f32x8 f;
-    f[0] = a[0]; f[1] = a[1]; f[2] = a[2]; f[3] = a[3];
-    f[4] = b[0]; f[5] = b[1]; f[6] = b[2]; f[7] = b[3];
-    return f;
   }
 }
 
@@ -257,9 +227,9 @@ __global__ __launch_bounds__(WM * WN * 64, (NSTG && (WM * TM + WN * TN) * 32 * 1
       const T* wsrc = wp + (long)(jt * a.J + j) * a.Cout_pad * a.Cin_pad + c * KC;
       char* base = smem + stage * STG;
 #pragma unroll
-      for (int q = 0; q < AI; ++q) gdma16(in + a_src[q] + joff, glds_off(base + (wave * AI + q) * 1024));
+      for (int q = 0; q < AI; ++q) glds16(in + a_src[q] + joff, lds_u32(base + (wave * AI + q) * 1024));
 #pragma unroll
-      for (int q = 0; q < BI; ++q) gdma16(wsrc + b_src[q], glds_off(base + A_B + (wave * BI + q) * 1024));
+      for (int q = 0; q < BI; ++q) glds16(wsrc + b_src[q], lds_u32(base + A_B + (wave * BI + q) * 1024));
     };
 #pragma unroll
     for (int sidx = 0; sidx < NSTG - 1; ++sidx)
@@ -513,23 +483,8 @@ __global__ void gconv_weights_kernel(const float* __restrict__ A, const float* _
 // dWeff[w][j][co][ci] += sum_i dy[(i,w)][co] * x[(i, nbr[w][j])][ci].  Block = (pair (w,j), 64-co x
 // 64-ci block, row range); the 4 waves split the k-steps of each 128-row tile and are summed in LDS
 // at the end; per-block partials go to a slab and are reduced deterministically.
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 constexpr int WKM = 128;  // rows per tile
-constexpr int WPR = 64;   // bytes per bf16 panel row (32 channels)
-
-DEV bf16x8 trfrag(const char* panel, int row0, int lane) {
-  const int i = lane & 15, gq = lane >> 4;
-  const int q = i >> 2, p = i & 3, h = gq >> 1;
-  const char* a0 = panel + (row0 + 8 * h + q) * WPR + (16 * (gq & 1) + 4 * p) * 2;
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(a0));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(a0 + 4 * WPR));
-  s16x8 v;
-  v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-  v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-  return __builtin_bit_cast(bf16x8, v);
-}
+constexpr int WPR = 64;   // bytes per bf16 panel row (32 channels): the packed panel trfrag reads
 
 struct WGG {
   int ntile, tpb, R, nco, nci;
@@ -822,24 +777,6 @@ __global__ __launch_bounds__(COB / 16 * 64, COB == 64 ? 3 : 1) void gconv_wgrad2
 constexpr int w3_stage(int deg) { return (2 + 2 * deg) * 32 * WPR; }
 constexpr int w3d(int deg, int lds) { return lds / w3_stage(deg) > 8 ? 8 : lds / w3_stage(deg); }
 
-template <int N, typename F>
-DEV void sfor(F&& f) {
-  [&]<int... I>(std::integer_sequence<int, I...>) { (f.template operator()<I>(), ...); }(
-      std::make_integer_sequence<int, N>{});
-}
-
-DEV unsigned lds_u32(const void* p) { return (unsigned)(size_t)(const __attribute__((address_space(3))) char*)p; }
-
-// 16 B per lane, global -> LDS at M0 = lds_off (lane-linear).  m0 is a reserved register, so it is not
-// declared clobbered: the asm saves the compiler's m0 in an SGPR it owns and restores it after the
-// issue (the DMA samples M0 when it is issued).
-DEV void glds16m(const void* src, unsigned lds_off) {
-  unsigned saved;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t"
-               "s_mov_b32 m0, %0"
-               : "=&s"(saved) : "v"(src), "s"(__builtin_amdgcn_readfirstlane(lds_off)) : "memory");
-}
-
 // half: -1 = a whole (joint, group, row range) block; 0 / 1 = one half of a split direct-plan block (tiles t0..t1)
 template <int DEG, int LDSB>
 DEV void wgrad3_body(const stgcn_gconv_wgrad_desc& a, const WGG& g, char* smem, int w, int rr, int grp, int t0,
@@ -865,9 +802,9 @@ DEV void wgrad3_body(const stgcn_gconv_wgrad_desc& a, const WGG& g, char* smem, 
   auto issue = [&](int t) {
     const int i = min(t * 32 + prow, a.NT - 1);  // rows past NT: clamped here, zeroed in LDS below
     const unsigned slot = ring + (unsigned)(((t - t0) % D) * STAGE) + woff;
-    glds16m(ysrc + i * ystep, slot);
+    glds16(ysrc + i * ystep, slot);
 #pragma unroll
-    for (int j = 0; j < DEG; ++j) glds16m(xsrc[j] + i * xstep, slot + (unsigned)((2 + 2 * j) * PANEL));
+    for (int j = 0; j < DEG; ++j) glds16(xsrc[j] + i * xstep, slot + (unsigned)((2 + 2 * j) * PANEL));
   };
 #pragma unroll
   for (int k = 0; k < D - 1; ++k)
@@ -888,7 +825,7 @@ DEV void wgrad3_body(const stgcn_gconv_wgrad_desc& a, const WGG& g, char* smem, 
 
   for (int t = t0; t < t1; ++t) {
     const int after = min(D - 2, t1 - 1 - t);  // tiles issued after t
-    sfor<D - 1>([&]<int m>() {
+    static_for<D - 1>([&]<int m>() {
       if (after == m) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(m * NU) : "memory");
     });
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -1106,9 +1043,9 @@ DEV void wgrad3w_body(const stgcn_gconv_wgrad_desc& a, const WGG& g, char* smem,
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int i = min(t * 32 + 16 * h + prow, a.NT - 1);  // rows past NT: clamped here, dy zeroed in LDS below
-      glds16m(ysrc + i * ystep, slot + (unsigned)(h * 1024));
+      glds16(ysrc + i * ystep, slot + (unsigned)(h * 1024));
 #pragma unroll
-      for (int j = 0; j < DEG; ++j) glds16m(xsrc[j] + i * xstep, slot + (unsigned)((4 + 4 * j) * PANEL + h * 1024));
+      for (int j = 0; j < DEG; ++j) glds16(xsrc[j] + i * xstep, slot + (unsigned)((4 + 4 * j) * PANEL + h * 1024));
     }
   };
 #pragma unroll
@@ -1138,7 +1075,7 @@ DEV void wgrad3w_body(const stgcn_gconv_wgrad_desc& a, const WGG& g, char* smem,
 
   for (int t = t0; t < t1; ++t) {
     const int after = min(D - 2, t1 - 1 - t);  // tiles issued after t
-    sfor<D - 1>([&]<int m>() {
+    static_for<D - 1>([&]<int m>() {
       if (after == m) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(m * NU) : "memory");
     });
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");

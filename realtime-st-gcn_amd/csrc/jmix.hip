@@ -21,6 +21,7 @@
 // completes in order: waiting behind a store's write latency per item had serialised the waves).
 // Output: lane = output joint, 4 consecutive channels per store.
 #include "common.h"
+#include "lds_ops.h"
 #include <type_traits>
 
 namespace {
@@ -43,49 +44,6 @@ template <> struct JT<float> {
   static constexpr int KS = 16;      // k-steps of 2 joints
   static constexpr int PANEL = 32 * 128;
 };
-
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
-// A operand (m = channel, k = 16 joints from row0) of a 32x32x16 MFMA from a [row][32 ch] bf16 panel
-DEV bf16x8 trfrag16(const char* panel, int row0, int lane) {
-  const int i = lane & 15, gq = lane >> 4;
-  const int q = i >> 2, p = i & 3, h = gq >> 1;
-  const char* a0 = panel + (row0 + 8 * h + q) * 64 + (16 * (gq & 1) + 4 * p) * 2;
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(a0));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(a0 + 4 * 64));
-  typedef short s16x8 __attribute__((ext_vector_type(8)));
-  s16x8 v;
-  v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-  v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-  return __builtin_bit_cast(bf16x8, v);
-}
-
-// 16 B per lane, global -> LDS (lane-linear from lds_off).  Issued from asm so the compiler does not treat
-// later LDS reads as aliasing the copy and drain vmcnt before each of them (the ring would serialise);
-// ordering is by the explicit vmcnt waits.  m0 is saved and restored inside the asm (never clobbered).
-DEV void dma16(const void* src, unsigned lds_off) {
-  unsigned saved;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t"
-               "s_mov_b32 m0, %0"
-               : "=&s"(saved) : "v"(src), "s"(__builtin_amdgcn_readfirstlane(lds_off)) : "memory");
-}
-DEV unsigned lds_u32(const void* p) { return (unsigned)(size_t)(const __attribute__((address_space(3))) char*)p; }
-
-// s_waitcnt vmcnt(n) for a wave-uniform run-time n (clamped to 63; waiting for fewer is always safe)
-template <int N>
-DEV void wait_vm_upto(int n) {
-  if constexpr (N < 63) {
-    if (n <= N) {
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-      return;
-    }
-    wait_vm_upto<N + 1>(n);
-  } else {
-    asm volatile("s_waitcnt vmcnt(63)" ::: "memory");
-  }
-}
-DEV void wait_vm(int n) { wait_vm_upto<0>(n < 0 ? 0 : n); }
 
 struct JmixArgs {
   const void* in;
@@ -146,7 +104,7 @@ __global__ __launch_bounds__(NWJ * 64) void jmix_kernel(const JmixArgs a) {
       for (int rr = 0; rr < 32; rr += RPI) {
         const int row = rr + lrow;
         const bool ok = row < V && uok;
-        dma16(ok ? src0 + (long)row * a.in_ld + cb + lunit * (16 / ELT) : src0, pan + rr * 32 * ELT);
+        glds16(ok ? src0 + (long)row * a.in_ld + cb + lunit * (16 / ELT) : src0, pan + rr * 32 * ELT);
       }
     }
     if constexpr (ACC) {  // the old output block [V rows][32 channels], read back in the flush from LDS
@@ -157,7 +115,7 @@ __global__ __launch_bounds__(NWJ * 64) void jmix_kernel(const JmixArgs a) {
       for (int rr = 0; rr < 32; rr += RPI) {
         const int row = rr + lrow;
         const bool ok = row < V && uok;
-        dma16(ok ? o0 + (long)row * a.out_ld + lunit * (16 / ELT) : o0, pan + rr * 32 * ELT);
+        glds16(ok ? o0 + (long)row * a.out_ld + lunit * (16 / ELT) : o0, pan + rr * 32 * ELT);
       }
     }
   };
@@ -298,7 +256,7 @@ __global__ __launch_bounds__(NWJ * 64) void jmix_kernel(const JmixArgs a) {
         if constexpr (sizeof(T) == 2) {
 #pragma unroll
           for (int ks = 0; ks < KS; ++ks) {
-            bf16x8 af = trfrag16(pan, 16 * ks, lane);
+            bf16x8 af = trfrag(pan, 16 * ks, lane);
             if (!mok) af = bf16x8{};
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bh[p][ks], acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bl[p][ks], acc, 0, 0, 0);

@@ -30,9 +30,9 @@
 // 8s+11 of the run) and 8 being written for step s+1; one block barrier per step hands them over.
 // Training forward: the kernel also writes g, u = z (pre-LN2), h and both LN statistics for the backward.
 #include "common.h"
+#include "lds_ops.h"
 #include "../../include/stgcn_amd.h"
 #include <stdlib.h>
-#include <utility>
 
 namespace {
 
@@ -74,43 +74,8 @@ constexpr int TARGET_BLOCKS = 256;     // MI355X CUs: runs per sample = 256 / N
 constexpr int LDS_MAX = 160 * 1024;
 static_assert(CF * VMAX <= 2 * RT * 32, "row tiles");
 
-template <int N, typename F>
-DEV void static_for(F&& f) {
-  [&]<int... I>(std::integer_sequence<int, I...>) { (f.template operator()<I>(), ...); }(
-      std::make_integer_sequence<int, N>{});
-}
-
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x2n __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
-// A operand of a 32x32x16 MFMA (m = channel, k = joint row) from a [row][32 ch] panel (gcn_tile.hip)
-DEV bf16x8 trfrag(const char* panel, int row0, int lane) {
-  const int i = lane & 15, gq = lane >> 4;
-  const int q = i >> 2, p = i & 3, h = gq >> 1;
-  const char* a0 = panel + (row0 + 8 * h + q) * 64 + (16 * (gq & 1) + 4 * p) * 2;
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(a0));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(a0 + 4 * 64));
-  typedef short s16x8 __attribute__((ext_vector_type(8)));
-  s16x8 v;
-  v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-  v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-  return __builtin_bit_cast(bf16x8, v);
-}
-
-// 16 B per lane, global -> LDS (lane-linear at M0 = lds_off), issued from asm so the compiler does not
-// drain vmcnt before every later LDS read; m0 is saved and restored inside the asm (never clobbered).
-DEV void glds16(const void* src, unsigned lds_off) {
-  unsigned saved;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t"
-               "s_mov_b32 m0, %0"
-               : "=&s"(saved) : "v"(src), "s"(lds_off) : "memory");
-}
-// Block barrier for the LDS hand-offs only: waits for this wave's LDS ops, NOT its outstanding global
-// loads, DMA and stores (__syncthreads() would drain vmcnt: the weight-fragment ring, the next batch's
-// x DMA and the z stores would all be waited for at every step).
-DEV void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // Sum over the 32 lanes of each wave half (lanes 0-31, 32-63) with DPP (VALU only, no LDS crossbar): the
 // totals land in lanes 31 and 63.
@@ -134,8 +99,6 @@ DEV float wave_total(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 31)) +
          __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }
-
-DEV unsigned lds_u32(const void* p) { return (unsigned)(size_t)(const __attribute__((address_space(3))) char*)p; }
 
 struct FGeom {
   int runs_n;  // runs per sample
@@ -237,8 +200,8 @@ __global__ __launch_bounds__(NW * 64, 1) void layer_fused_kernel(const stgcn_lay
 #pragma unroll
         for (int cb = 0; cb < G; ++cb) {
           const unsigned dst = ring0 + (unsigned)((i * G + cb) * PANEL);
-          glds16(src + cb * 32, dst);
-          if (row2) glds16(src + cb * 32 + 16L * a.x_ld, dst + 1024);
+          glds16_sgpr(src + cb * 32, dst);
+          if (row2) glds16_sgpr(src + cb * 32 + 16L * a.x_ld, dst + 1024);
         }
       }
     };

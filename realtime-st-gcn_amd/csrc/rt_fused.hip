@@ -18,6 +18,7 @@
 // Rows are channels-last [V][C] fp32 (the layout of the rest of the package); FIFO state [fifo][V][C],
 // accumulators [S][V][C], indices int[2] (fifo, acc) — device buffers, so a HIP graph can replay frames.
 #include "common.h"
+#include "frame_ops.h"
 #include "../../include/stgcn_amd.h"
 
 namespace {
@@ -27,18 +28,6 @@ constexpr int CB = 2;        // output channels per rt_gcn block (Cout / 2 block
 constexpr int VMAX = 32;
 constexpr int CMAX = 256;
 constexpr int PMAX = 3;
-
-// fixed-order block sum (NT threads): every thread gets the total
-DEV float block_sum(float v, float* red) {
-  v = wave_sum(v);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) red[w] = v;
-  __syncthreads();
-  float t = 0.f;
-  for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t += red[i];
-  return t;
-}
 
 // LayerNorm statistics (mean, 1/sqrt(unbiased var + eps)) of n values (two passes over the data)
 DEV float2 ln_stats(const float* x, int n, float eps, float* red) {
@@ -74,24 +63,6 @@ __global__ __launch_bounds__(NT) void rt_in_kernel(const float* __restrict__ x, 
     for (int c = 0; c < 3; ++c) s = fmaf(W[co * 3 + c], xs[c * V + v], s);
     out[i] = s;
   }
-}
-
-// 8 lanes per dot product of length Cin (float4 k = kk + 8j: one contiguous 128-B piece per step),
-// butterfly-summed; w from global (L2), x from LDS
-DEV float dot8(const float* __restrict__ w, const float* x, int K4, int kk) {
-  const float4* w4 = reinterpret_cast<const float4*>(w);
-  const float4* x4 = reinterpret_cast<const float4*>(x);
-  float s = 0.f;
-  for (int k = kk; k < K4; k += 8) {
-    const float4 a = w4[k], b = x4[k];
-    s = fmaf(a.x, b.x, s);
-    s = fmaf(a.y, b.y, s);
-    s = fmaf(a.z, b.z, s);
-    s = fmaf(a.w, b.w, s);
-  }
-#pragma unroll
-  for (int m = 1; m < 8; m <<= 1) s += __shfl_xor(s, m);
-  return s;
 }
 
 // conv first, as the reference (tgcn: conv1x1 then @A): y_p[u][co] = W_p[co] . x[u] for the block's CB
@@ -448,11 +419,6 @@ DEV void rf_ln_prefetch(const stgcn_rt_layer& ly, int n4, RfLn& p) {
 // kernel-argument (wave-uniform) values
 DEV float4 ld_wt4(__amdgpu_buffer_rsrc_t r, int e4) {
   return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r, e4 * 16, 0, 16));
-}
-DEV float sum4(float4 v) { return (v.x + v.y) + (v.z + v.w); }
-DEV float sq4(float4 v, float m) {
-  const float a = v.x - m, b = v.y - m, c = v.z - m, d = v.w - m;
-  return fmaf(a, a, fmaf(b, b, fmaf(c, c, d * d)));
 }
 
 // dynamic LDS carve (floats): xs [VMAX*CMAX] (the current layer's input), wsm, ys, As, red, idx

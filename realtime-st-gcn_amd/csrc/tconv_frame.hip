@@ -14,29 +14,14 @@
 // joints).  The data gradient of the 64-channel layers ships on this kernel; a frame-per-step form
 // for 25 < V <= 32 was removed in round 6 (no skeleton needs it).
 #include "common.h"
+#include "lds_ops.h"
 #include "../../include/stgcn_amd.h"
-#include <utility>
 
 namespace {
 
 constexpr int C = 64, KT = 9, HALO = 4;
 
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
-DEV unsigned lds_u32(const void* p) { return (unsigned)(size_t)(const __attribute__((address_space(3))) char*)p; }
-
-DEV void glds16(const void* src, unsigned lds_off) {
-  unsigned saved;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t"
-               "s_mov_b32 m0, %0"
-               : "=&s"(saved) : "v"(src), "s"(__builtin_amdgcn_readfirstlane(lds_off)) : "memory");
-}
-
-template <int N, typename F>
-DEV void sfor(F&& f) {
-  [&]<int... I>(std::integer_sequence<int, I...>) { (f.template operator()<I>(), ...); }(
-      std::make_integer_sequence<int, N>{});
-}
 
 // ------------------------------------------------------------------------------------------------------------
 // Row-streaming form: the block's output rows
@@ -245,7 +230,7 @@ __global__ __launch_bounds__(RW * 64, 1) void tcr_kernel(const stgcn_conv_desc a
     fb[1][0] = hread(0, 1);
     fb[1][1] = hread(1, 1);
     const bool prev = s >= 1;
-    if (!(TDBG & 1)) sfor<KSTEPS>([&]<int k>() {
+    if (!(TDBG & 1)) static_for<KSTEPS>([&]<int k>() {
       constexpr int k2 = k + 2;
       if constexpr (k2 < KSTEPS) {
         if constexpr ((k2 & 3) == 0) tap_addr(k2 >> 2);

@@ -11,6 +11,7 @@
 //   * per-block fp32 partials go to a slab, summed over the chunks in a fixed order (deterministic).
 // Served: bf16, M % 32 == 0, Cin and Cout multiples of 32, 16-B aligned rows; else the frame-tiled kernel.
 #include "common.h"
+#include "lds_ops.h"
 #include "../../include/stgcn_amd.h"
 
 namespace {
@@ -23,47 +24,6 @@ constexpr int GCO = 2, GCI_MAX = 8;
 constexpr int TPW = GCO * GCI_MAX / 4;  // tiles per wave (<= 4)
 constexpr int NSTAGE = 3;  // minimum ring depth
 constexpr int TARGET_BLOCKS = 512;
-
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
-DEV bf16x8 trfrag16(const char* panel, int row0, int lane) {
-  const int i = lane & 15, gq = lane >> 4;
-  const int q = i >> 2, p = i & 3, h = gq >> 1;
-  const char* a0 = panel + (row0 + 8 * h + q) * 64 + (16 * (gq & 1) + 4 * p) * 2;
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(a0));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(a0 + 4 * 64));
-  typedef short s16x8 __attribute__((ext_vector_type(8)));
-  s16x8 v;
-  v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-  v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-  return __builtin_bit_cast(bf16x8, v);
-}
-
-// global -> LDS, lane-linear; asm so the compiler keeps no alias-driven vmcnt drains; m0 saved/restored
-DEV void dma16(const void* src, unsigned lds_off) {
-  unsigned saved;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t"
-               "s_mov_b32 m0, %0"
-               : "=&s"(saved) : "v"(src), "s"(__builtin_amdgcn_readfirstlane(lds_off)) : "memory");
-}
-DEV unsigned lds_u32(const void* p) { return (unsigned)(size_t)(const __attribute__((address_space(3))) char*)p; }
-
-// s_waitcnt vmcnt(n) for a wave-uniform run-time n (clamped to 63, the counter's range: waiting for fewer
-// outstanding operations is always safe)
-template <int N>
-DEV void wait_vm_upto(int n) {
-  if constexpr (N < 63) {
-    if (n <= N) {
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-      return;
-    }
-    wait_vm_upto<N + 1>(n);
-  } else {
-    asm volatile("s_waitcnt vmcnt(63)" ::: "memory");
-  }
-}
-DEV void wait_vm(int n) { wait_vm_upto<0>(n < 0 ? 0 : n); }
 
 struct W1Geom {
   long steps;    // M / 32
@@ -107,8 +67,8 @@ __global__ __launch_bounds__(NT1) void wgrad1x1_kernel(const stgcn_wgrad_desc a,
       }
       const bf16* r0 = src + (st * 32 + lrow) * (long)ld + lunit * 8;
       const unsigned dst = lds_u32(base + p * PANEL);
-      dma16(r0, dst);
-      dma16(r0 + 16L * ld, dst + 1024);
+      glds16(r0, dst);
+      glds16(r0 + 16L * ld, dst + 1024);
     }
   };
 
@@ -142,8 +102,8 @@ __global__ __launch_bounds__(NT1) void wgrad1x1_kernel(const stgcn_wgrad_desc a,
       const char* px = base + (nco + ib) * PANEL;
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
-        const bf16x8 fa = trfrag16(pdy, 16 * ks, lane);  // m = co, k = rows
-        const bf16x8 fb = trfrag16(px, 16 * ks, lane);   // n = ci, k = rows
+        const bf16x8 fa = trfrag(pdy, 16 * ks, lane);  // m = co, k = rows
+        const bf16x8 fb = trfrag(px, 16 * ks, lane);   // n = ci, k = rows
         acc[k] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, fb, acc[k], 0, 0, 0);
       }
     }

@@ -24,8 +24,8 @@
 //   * the fp32 block result goes to a slab [row range][9][Cout][Cin], summed in a fixed order by slab_reduce
 //     (wgrad_tile.hip): deterministic.
 #include "common.h"
+#include "lds_ops.h"
 #include "../../include/stgcn_amd.h"
-#include <utility>
 
 #ifndef WR_G64
 #define WR_G64 2
@@ -71,37 +71,6 @@ DEV long long wr_time() {
   if constexpr (WR_PROF) return __builtin_amdgcn_s_memtime();
   return 0;
 }  // DMA source of rows outside the sample / the run (zero-initialised code object data)
-
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
-template <int N, typename F>
-DEV void sfor(F&& f) {
-  [&]<int... I>(std::integer_sequence<int, I...>) { (f.template operator()<I>(), ...); }(
-      std::make_integer_sequence<int, N>{});
-}
-
-DEV unsigned lds_u32(const void* p) { return (unsigned)(size_t)(const __attribute__((address_space(3))) char*)p; }
-
-// 16 B per lane, global -> LDS at M0 = lds_off (lane-linear); m0 saved / restored around the issue
-DEV void glds16(const void* src, unsigned lds_off) {
-  unsigned saved;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t"
-               "s_mov_b32 m0, %0"
-               : "=&s"(saved) : "v"(src), "s"(__builtin_amdgcn_readfirstlane(lds_off)) : "memory");
-}
-
-// MFMA fragment from a [rows][32 ch] panel: lane (c, h) gets rows r0 + 8h .. r0 + 8h + 7 of column c, as two
-// ds_read_b64_tr_b16 (rows +q and +q+4); p = panel + r0 * PR (uniform), loff = the lane's constant offset
-DEV bf16x8 trfrag(const char* p, int loff) {
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p + loff));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p + loff + 4 * PR));
-  s16x8 v;
-  v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-  v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-  return __builtin_bit_cast(bf16x8, v);
-}
 
 struct WRGeom {
   int runs_n, run;  // runs per sample, frames per run
@@ -312,11 +281,11 @@ __global__ __launch_bounds__(NT, 1) void wgrad_ring_kernel(const stgcn_wgrad_des
     bf16x8 fx[D + 1], fy[2];
     auto rd = [&]<int u>() {
       constexpr int ks = u / TW, t = u % TW;
-      if constexpr (t == 0) fy[ks & 1] = trfrag(Yl + 16 * ks * PR, 0);
-      if (t < ntap) fx[u % (D + 1)] = trfrag(Xl + (VT ? t * VT * PR : t * tb) + 16 * ks * PR, 0);
+      if constexpr (t == 0) fy[ks & 1] = trpair<PR>(Yl + 16 * ks * PR);
+      if (t < ntap) fx[u % (D + 1)] = trpair<PR>(Xl + (VT ? t * VT * PR : t * tb) + 16 * ks * PR);
     };
-    sfor<D>([&]<int u>() { rd.template operator()<u>(); });
-    sfor<NU>([&]<int u>() {
+    static_for<D>([&]<int u>() { rd.template operator()<u>(); });
+    static_for<NU>([&]<int u>() {
       if constexpr (u + D < NU) rd.template operator()<u + D>();
       constexpr int ks = u / TW, t = u % TW;
       if (t < ntap) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fy[ks & 1], fx[u % (D + 1)], acc[t], 0, 0, 0);

@@ -17,31 +17,14 @@
 // is reused by every tap), so the only output traffic is one fp32 partial per block: written to a
 // workspace slab with plain stores, then summed deterministically into dW by a second kernel.
 #include "common.h"
+#include "lds_ops.h"
 #include <stdlib.h>
 #include "../../include/stgcn_amd.h"
 
 namespace {
 
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
 constexpr int KM = 128;      // rows (K) per tile
-constexpr int PR = 64;       // bytes per panel row (32 bf16 channels)
-
-// MFMA operand fragment from a [rows][32] bf16 panel: lane (c = lane&31, h = lane>>5) gets
-// panel[row0 + 8h + j][c], j = 0..7, via two ds_read_b64_tr_b16 (4 rows each).
-DEV bf16x8 trfrag(const char* panel, int row0, int lane) {
-  const int i = lane & 15, g = lane >> 4;
-  const int q = i >> 2, p = i & 3, h = g >> 1;
-  const char* a0 = panel + (row0 + 8 * h + q) * PR + (16 * (g & 1) + 4 * p) * 2;
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(a0));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(a0 + 4 * PR));
-  s16x8 v;
-  v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-  v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-  return __builtin_bit_cast(bf16x8, v);
-}
+constexpr int PR = 64;       // bytes per panel row (32 bf16 channels): the packed panel trfrag reads
 
 struct WGeom {
   int F;          // frames per tile (0 = flat)

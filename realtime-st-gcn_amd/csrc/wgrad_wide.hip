@@ -23,9 +23,9 @@
 //   * the fp32 block result goes to a slab [range][9][Cout][Cin], summed deterministically into dW by
 //     slab_reduce (wgrad_tile.hip).
 #include "common.h"
+#include "lds_ops.h"
 #include "../../include/stgcn_amd.h"
 #include <stdlib.h>
-#include <utility>
 
 namespace {
 
@@ -38,29 +38,6 @@ constexpr int DY_BYTES = (COB / 32) * DY_PANEL;  // 32 KB per buffer
 constexpr int DY_U = KM * (COB / 8) / NT;        // 16-B dY units per thread per tile (4)
 constexpr int X_U = (KM * (CIB / 8) + NT - 1) / NT;  // input units per thread per batch of <= 128 rows (2)
 constexpr int LDS_MAX = 160 * 1024;
-
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
-template <int N, typename F>
-DEV void static_for(F&& f) {
-  [&]<int... I>(std::integer_sequence<int, I...>) { (f.template operator()<I>(), ...); }(
-      std::make_integer_sequence<int, N>{});
-}
-
-DEV void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// two ds_read_b64_tr_b16 (rows lo and lo + 4 of a 64-B-row panel) -> one MFMA fragment: lane
-// (c = column, h) receives rows 8h .. 8h+7 of its column
-DEV bf16x8 trpair(const char* lo) {
-  const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)lo);
-  const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(lo + 4 * PR));
-  s16x8 v;
-  v[0] = a[0]; v[1] = a[1]; v[2] = a[2]; v[3] = a[3];
-  v[4] = b[0]; v[5] = b[1]; v[6] = b[2]; v[7] = b[3];
-  return __builtin_bit_cast(bf16x8, v);
-}
 
 struct WWGeom {
   int F;         // output frames per tile
@@ -238,8 +215,8 @@ __global__ __launch_bounds__(NT, 1) void wgrad_wide_kernel(const stgcn_wgrad_des
     bf16x8 fx[D + 1], fy[2];
     auto rd = [&]<int u>() {
       constexpr int ks = u / KT, t = u % KT;
-      if constexpr (t == 0) fy[ks & 1] = trpair(Y + 16 * ks * PR);
-      fx[u % (D + 1)] = trpair(X + t * tb + 16 * ks * PR);
+      if constexpr (t == 0) fy[ks & 1] = trpair<PR>(Y + 16 * ks * PR);
+      fx[u % (D + 1)] = trpair<PR>(X + t * tb + 16 * ks * PR);
     };
     static_for<D>([&]<int u>() { rd.template operator()<u>(); });
     static_for<NU>([&]<int u>() {
