@@ -33,7 +33,8 @@ extern "C" {
  *      stgcn_gconv_wgrad_desc gained phase);
  *   5: round 6 (stgcn_bn_merge: one (count, mean, M2) entry per channel, the SyncBatchNorm exchange unit);
  *   6: stgcn_co_* + stgcn_co_layer: CoST-GCN per-frame inference (co_frame.hip);
- *   7: stgcn_ms_* + stgcn_ms_layer / stgcn_ms_lin: MS-TCN stages, forward and backward (ms_stage.hip). */
+ *   7: stgcn_ms_* + stgcn_ms_layer / stgcn_ms_lin: MS-TCN stages, forward and backward (ms_stage.hip);
+ *      still 7: stgcn_rt_streams* added (rt_streams.hip) — additive, no existing struct or entry point changed. */
 #define STGCN_ABI_VERSION 7
 
 /* Implicit-GEMM (Kt x 1) row convolution; see conv_rows.hip for the exact contract.
@@ -477,6 +478,54 @@ typedef struct {
   stgcn_rt_layer layers[STGCN_RT_MAX_LAYERS];
 } stgcn_rt_frame_desc;
 int stgcn_rt_frame(const stgcn_rt_frame_desc* d, void* stream);
+
+/* A batch of B independent skeleton streams of the same LayerNorm RT-ST-GCN, each advanced by one frame in ONE launch
+ * (rt_streams.hip; additive to ABI 7).  One workgroup of 512 threads per stream runs stgcn_rt_frame's arithmetic for
+ * its stream (input LayerNorm + fcn_in; per layer conv1x1, A-mix over P, FIFO step, residual, LayerNorm, ReLU, index
+ * advance; pool + fcn_out) with the layer input / output in LDS: no workgroup waits on another (no grid barrier, no
+ * atomics, no cooperative launch), so B may exceed the CU count.  The conv and the A-mix run on the fp32 matrix cores
+ * (v_mfma_f32_32x32x2_f32, exact fp32 products, fixed summation order; LayerNorm statistics two-pass in a fixed
+ * order): a stream's result does not depend on B, on its slot or on the other streams.
+ * State is stream-major and updated in place: fifo [B][fifo_size][V][Cout], acc [B][S][V][Cout], idx [B][2].
+ * active [B] (device int32, read by the kernel): 0 = skip (state untouched, the out row written as zeros), 2 = restart
+ * then step (FIFO, accumulators and indices taken as zero before this frame; the kernel clears them), any other
+ * value = step.
+ * wp: stgcn_rt_streams_pack_weight(w [P*Cout][Cin], groups = P, rows = Cout) — per partition the MFMA B-fragment image
+ * [Cout/32 tiles][Cin/16 k-steps][64 lanes][8] of stgcn_co_pack_weight; wrp: the same of wr [Cout][Cin] (groups = 1),
+ * res_mode 2 only.  The unpacked weights are not read.
+ * Limits of stgcn_rt_frame: 2 <= V <= 32, 4 <= C <= 256 (C % 4 == 0), V * C <= 7680, P <= 3, L <= STGCN_RT_MAX_LAYERS,
+ * res_mode 1 needs Cin == Cout; B >= 1.  A NULL required pointer or a shape outside the limits returns 1 before any
+ * launch. */
+typedef struct {
+  int Cin, Cout, P, fifo_size, S, res_mode;
+  const float* A;       /* [P][V][V] graph * importance */
+  const float* wp;      /* packed conv weight, P * stgcn_rt_streams_pack_elems(Cout, Cin) floats */
+  const float* bias2d;  /* [V][Cout] or NULL */
+  const float* wrp;     /* packed residual conv weight (res_mode 2) or NULL */
+  const float* ln_w;    /* [V][Cout], as stgcn_rt_layer */
+  const float* ln_b;
+  const float* lnr_w;   /* residual LN (res_mode 2), [V][Cout] */
+  const float* lnr_b;
+  float* fifo;          /* [B][fifo_size][V][Cout] */
+  float* acc;           /* [B][S][V][Cout] */
+  int* idx;             /* [B][2] (fifo, acc) */
+} stgcn_rt_streams_layer;
+typedef struct {
+  int V, L, C0, K, B, pad_;
+  const float* x;       /* [B][3][V] */
+  const int* active;    /* [B] */
+  const float* ln_w;    /* [3*V] */
+  const float* ln_b;
+  const float* w_in;    /* [C0][3] */
+  const float* b_in;    /* [C0] */
+  const float* w_out;   /* [K][C_last] */
+  const float* b_out;   /* [K] or NULL */
+  float* out;           /* [B][K] */
+  stgcn_rt_streams_layer layers[STGCN_RT_MAX_LAYERS];
+} stgcn_rt_streams_desc;
+long stgcn_rt_streams_pack_elems(int rows, int Cin);
+int stgcn_rt_streams_pack_weight(const float* w, int groups, int rows, int Cin, float* dst, void* stream);
+int stgcn_rt_streams(const stgcn_rt_streams_desc* d, void* stream);
 
 /* CoST-GCN per-frame inference (models/costgcn/costgcn.py:192-211; co_frame.hip), batch 1, one frame per call,
  * LayerNorm layers.  A layer keeps a ring of the last fifo = S*(Kt-1)+1 frames of ReLU(LN1(gcn(x))) (tcn.0 is per

@@ -102,6 +102,18 @@ class RtFrameDesc(ctypes.Structure):
                [("layers", RtLayer * RT_MAX_LAYERS)]
 
 
+class RtStreamsLayer(ctypes.Structure):  # stgcn_rt_streams_layer
+    _fields_ = [(n, c_int) for n in ("Cin", "Cout", "P", "fifo_size", "S", "res_mode")] + \
+               [(n, c_void_p) for n in ("A", "wp", "bias2d", "wrp", "ln_w", "ln_b", "lnr_w", "lnr_b", "fifo", "acc",
+                                        "idx")]
+
+
+class RtStreamsDesc(ctypes.Structure):  # stgcn_rt_streams_desc
+    _fields_ = [(n, c_int) for n in ("V", "L", "C0", "K", "B", "pad_")] + \
+               [(n, c_void_p) for n in ("x", "active", "ln_w", "ln_b", "w_in", "b_in", "w_out", "b_out", "out")] + \
+               [("layers", RtStreamsLayer * RT_MAX_LAYERS)]
+
+
 class CoLayer(ctypes.Structure):  # stgcn_co_layer
     _fields_ = [(n, c_int) for n in ("V", "Cin", "Cout", "P", "Kt", "S", "res_mode", "dtype", "splits", "pad_")] + \
                [(n, c_void_p) for n in ("x", "A", "w", "bias2d", "wr", "br", "ln1_w", "ln1_b", "ln2_w", "ln2_b",
@@ -199,6 +211,9 @@ _SIGS = {
                                     c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "stgcn_rt_frame_out": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "stgcn_rt_frame": (c_int, [ctypes.POINTER(RtFrameDesc), c_void_p]),
+    "stgcn_rt_streams_pack_elems": (c_long, [c_int, c_int]),
+    "stgcn_rt_streams_pack_weight": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "stgcn_rt_streams": (c_int, [ctypes.POINTER(RtStreamsDesc), c_void_p]),
     "stgcn_co_pack_elems": (c_long, [c_int, c_int, c_int]),
     "stgcn_co_pack_weight": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "stgcn_co_splits": (c_int, [ctypes.POINTER(CoLayer), c_void_p]),

@@ -113,6 +113,9 @@ int co_check(const stgcn_co_layer& d, bool shapes_only);
 int co_num_splits(const stgcn_co_layer& d, hipStream_t s);
 long co_pack_elems(int Cout, int C, int Kt);
 int co_pack_launch(const float* w, int Cout, int C, int Kt, void* dst, int dtype, hipStream_t s);
+long co_pack_rows_elems(int rows, int C);
+int co_pack_rows_launch(const float* w, int groups, int rows, int C, float* dst, hipStream_t s);
+int rt_streams_launch(const stgcn_rt_streams_desc& d, hipStream_t s);
 int co_gcn_launch(const stgcn_co_layer& d, hipStream_t s);
 int co_push_launch(const stgcn_co_layer& d, hipStream_t s);
 int co_taps_launch(const stgcn_co_layer& d, hipStream_t s);
@@ -460,6 +463,14 @@ int stgcn_rt_frame_out(const float* x, int V, int C, const float* w, const float
 }
 int stgcn_rt_frame(const stgcn_rt_frame_desc* d, void* stream) {
   return d ? rt_frame_launch(*d, STREAM(stream)) : STGCN_EBADSHAPE;
+}
+
+long stgcn_rt_streams_pack_elems(int rows, int Cin) { return co_pack_rows_elems(rows, Cin); }
+int stgcn_rt_streams_pack_weight(const float* w, int groups, int rows, int Cin, float* dst, void* stream) {
+  return co_pack_rows_launch(w, groups, rows, Cin, dst, STREAM(stream));
+}
+int stgcn_rt_streams(const stgcn_rt_streams_desc* d, void* stream) {
+  return d ? rt_streams_launch(*d, STREAM(stream)) : STGCN_EBADSHAPE;
 }
 
 long stgcn_co_pack_elems(int Cout, int C, int Kt) { return co_pack_elems(Cout, C, Kt); }

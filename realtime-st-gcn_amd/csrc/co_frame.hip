@@ -143,15 +143,6 @@ __global__ __launch_bounds__(FNT) void co_push_kernel(const stgcn_co_layer d) {
 }
 
 // ------------------------------------------------------------------------------------------- the tap GEMM
-DEV void load4(const float* p, float* f) {
-  const float4 v = *reinterpret_cast<const float4*>(p);
-  f[0] = v.x, f[1] = v.y, f[2] = v.z, f[3] = v.w;
-}
-DEV void load4(const bf16* p, bf16* f) {
-  const bf16x4 v = *reinterpret_cast<const bf16x4*>(p);
-  f[0] = v[0], f[1] = v[1], f[2] = v[2], f[3] = v[3];
-}
-
 // A fragment of k-step ks: lane (row = l & 31, h = l >> 5) holds kk = 16 ks + 8 h + j, j < 8, of frame row `row`,
 // kk = tap * C + ci read from ring slot (head + tap * S) % fifo.  Two 4-element units (C % 4 == 0: one slot each).
 template <typename T>
@@ -174,24 +165,6 @@ DEV typename Tr<T>::frag load_a(const T* __restrict__ ring, int ks, int ks1, int
 #pragma unroll
   for (int j = 0; j < 8; ++j) a[j] = f[j];
   return a;
-}
-
-// B fragment: 8 contiguous packed elements at (ks * 64 + lane) * 8 of the column tile's panel
-template <typename T>
-DEV typename Tr<T>::frag load_b(const T* __restrict__ panel, int ks, int ks1, int lane) {
-  T f[8];
-  if (ks < ks1) {
-    const T* p = panel + ((long)ks * 64 + lane) * 8;
-    load4(p, f);
-    load4(p + 4, f + 4);
-  } else {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) f[i] = (T)0.f;
-  }
-  typename Tr<T>::frag b;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) b[j] = f[j];
-  return b;
 }
 
 constexpr int TW = NT / 64;  // waves per co_taps block; wave w takes k-steps ks0 + w, ks0 + w + TW, ...
@@ -349,6 +322,23 @@ int co_pack_launch(const float* w, int Cout, int C, int Kt, void* dst, int dtype
   else
     hipLaunchKernelGGL(co_pack_kernel<bf16>, dim3(nb), dim3(NT), 0, s, w, Cout, C, Kt, num_ksteps(C, Kt), total,
                        (bf16*)dst);
+  return hipGetLastError() == hipSuccess ? STGCN_OK : STGCN_EHIP;
+}
+
+// The same [tile][k-step][lane][8] image for `groups` consecutive row-major fp32 matrices [rows][C] (a 1x1 conv weight,
+// one group per partition; Kt = 1, so kk = ci): each group is packed on its own, so no 32-row tile straddles two groups.
+long co_pack_rows_elems(int rows, int C) {
+  if (rows < 1 || rows > CMAX || C < 4 || C > CMAX || C % 4) return -1;
+  return (long)((rows + 31) / 32) * num_ksteps(C, 1) * 512;
+}
+
+int co_pack_rows_launch(const float* w, int groups, int rows, int C, float* dst, hipStream_t s) {
+  const long total = co_pack_rows_elems(rows, C);
+  if (!w || !dst || total < 0 || groups < 1 || groups > PMAX) return STGCN_EBADSHAPE;
+  const unsigned nb = (unsigned)((total + NT - 1) / NT);
+  for (int g = 0; g < groups; ++g)
+    hipLaunchKernelGGL(co_pack_kernel<float>, dim3(nb), dim3(NT), 0, s, w + (long)g * rows * C, rows, C, 1,
+                       num_ksteps(C, 1), total, dst + g * total);
   return hipGetLastError() == hipSuccess ? STGCN_OK : STGCN_EHIP;
 }
 

@@ -1,0 +1,283 @@
+// RT-ST-GCN per-frame inference for a batch of B independent skeleton streams (stgcn_rt_streams), fp32, LayerNorm
+// online layers: one workgroup per stream runs the whole network for its stream's frame (rt_fused.hip's arithmetic:
+// rt_in / rt_gcn / rt_norm / rt_out) with the layer input and output in LDS, the weights streamed from L2 (shared
+// by every workgroup) and the stream's FIFO state updated in place.  No workgroup waits on another: no grid barrier,
+// no spin, no atomics.  B may exceed the CU count; the workgroups queue.
+//
+// Per layer (V <= 32 joint rows, zero-padded to the 32-row MFMA operand by the fragment loads):
+//   (1) tasks over the 8 waves: (partition p, 32-channel tile) of the conv, and (tile) of the residual conv.
+//       Y_p[u][co] = sum_ci x[u][ci] W[p*Cout+co][ci]: v_mfma_f32_32x32x2_f32, A operand = x rows from LDS, B operand =
+//       the packed weight image (co_frame.hip's [tile][k-step][lane][8]: 32 B per lane per 16-k step, read once).
+//       The A-mix runs on the accumulators where they are: accumulator register r of lane l holds Y_p[acc_row(r, l)][co],
+//       which IS the B operand (k = l >> 5, n = l & 31) of an MFMA whose two k are u = acc_row(r, 0) and acc_row(r, 32);
+//       with A operand A_p[u][v] (m = v) sixteen MFMAs give Z_p[v][co] = sum_u A_p[u][v] Y_p[u][co].
+//       Z_p -> LDS zs[p], the residual conv -> LDS rs.
+//   (2) z = bias2d + Z_0 + Z_1 + Z_2; a = acc[ai] + z - fifo[fi]; acc[ai] = a; fifo[fi] = z (rtstgcn.py:591-627);
+//       y = relu(relu(LN(a)) + res) (rt_norm_kernel's math; two-pass statistics, fixed-order sums) -> LDS xs.
+// Every sum has a fixed order that depends on the network only: a stream's frames are bit-identical whatever B, its
+// slot and the other streams' masks are.
+#include "common.h"
+#include "frame_ops.h"
+#include "../../include/stgcn_amd.h"
+
+namespace {
+
+constexpr int NT = 512;
+constexpr int NW = NT / 64;
+constexpr int VMAX = 32;
+constexpr int CMAX = 256;
+constexpr int PMAX = 3;
+constexpr int MAXE = 7680;                    // V * C limit (stgcn_rt_frame's)
+constexpr int XPAD = 4;                       // xs row stride = C + XPAD floats: the 32 rows of a fragment read spread over the banks
+constexpr int U4 = (MAXE / 4 + NT - 1) / NT;  // float4 units of a frame per thread
+constexpr int TU = 4;                         // k-steps in flight per wave
+constexpr int XS_FLOATS = MAXE + VMAX * XPAD;
+// dynamic LDS (floats): xs | rs | zs[PMAX] | red
+constexpr int LDS_FLOATS = XS_FLOATS + MAXE + PMAX * MAXE + 16;
+
+// A fragment of k-step ks: lane (row = l & 31, h = l >> 5) holds x[row][16 ks + 8 h + j], j < 8; zero rows beyond V
+DEV f32x8 load_a(const float* xs, int ld, int ks, int nks, int row, int h, int V, int Cin) {
+  float f[8];
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const int kk = ks * 16 + 8 * h + 4 * u;
+    if (ks < nks && row < V && kk < Cin) {
+      load4(xs + row * ld + kk, f + 4 * u);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) f[4 * u + i] = 0.f;
+    }
+  }
+  f32x8 a;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) a[j] = f[j];
+  return a;
+}
+
+DEV float4 relu4(float4 v) { return make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)); }
+DEV float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+// w * (a - mean) * rstd + b per element
+DEV float4 affine4(float4 a, float mean, float rstd, float4 w, float4 b) {
+  return make_float4(fmaf(w.x, (a.x - mean) * rstd, b.x), fmaf(w.y, (a.y - mean) * rstd, b.y),
+                     fmaf(w.z, (a.z - mean) * rstd, b.z), fmaf(w.w, (a.w - mean) * rstd, b.w));
+}
+
+// two-pass LayerNorm statistics (mean, 1 / sqrt(unbiased var + eps)) of the frame's n = 4 * n4 values in registers
+// (unit e4 = tid + NT * j)
+DEV float2 ln_stats_reg(const float4 (&v)[U4], int n4, float* red) {
+  const int tid = threadIdx.x;
+  float s = 0.f;
+#pragma unroll
+  for (int j = 0; j < U4; ++j) s += tid + NT * j < n4 ? sum4(v[j]) : 0.f;
+  const float n = 4.f * (float)n4;
+  const float mean = block_sum(s, red) / n;
+  float q = 0.f;
+#pragma unroll
+  for (int j = 0; j < U4; ++j) q += tid + NT * j < n4 ? sq4(v[j], mean) : 0.f;
+  const float var = block_sum(q, red) / (n - 1.f);
+  return make_float2(mean, 1.f / sqrtf(var + 1e-5f));
+}
+
+__global__ __launch_bounds__(NT) void rt_streams_kernel(const stgcn_rt_streams_desc d) {
+  extern __shared__ __attribute__((aligned(16))) float rs_sm[];
+  float* xs = rs_sm;            // [V][C + XPAD] the current layer's input
+  float* rs = xs + XS_FLOATS;   // [V][Cout] residual conv
+  float* zs = rs + MAXE;        // [P][V][Cout] A-mixed conv per partition; the heads' scratch
+  float* red = zs + PMAX * MAXE;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, V = d.V;
+  const long b = blockIdx.x;
+  const int code = d.active[b];
+  float* out = d.out + b * d.K;
+  if (code == 0) {  // skip: state untouched, a zero row (uniform over the workgroup)
+    for (int k = tid; k < d.K; k += NT) out[k] = 0.f;
+    return;
+  }
+  const bool restart = code == 2;
+  if (restart) {  // clear this stream's FIFOs and accumulators; every later write of them follows a barrier
+    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int l = 0; l < d.L; ++l) {
+      const stgcn_rt_streams_layer ly = d.layers[l];
+      const long E4 = (long)V * ly.Cout / 4;
+      float4* f = reinterpret_cast<float4*>(ly.fifo) + b * ly.fifo_size * E4;
+      float4* a = reinterpret_cast<float4*>(ly.acc) + b * ly.S * E4;
+      for (long i = tid; i < ly.fifo_size * E4; i += NT) f[i] = z4;
+      for (long i = tid; i < ly.S * E4; i += NT) a[i] = z4;
+    }
+  }
+
+  // input head: LayerNorm([3,1,V]) + fcn_in (rt_in_kernel's arithmetic)
+  {
+    float* xi = zs;
+    const int n = 3 * V, C0 = d.C0, ld = C0 + XPAD;
+    const float* x = d.x + b * n;
+    for (int i = tid; i < n; i += NT) xi[i] = x[i];
+    __syncthreads();
+    float s = 0.f;
+    for (int i = tid; i < n; i += NT) s += xi[i];
+    const float mean = block_sum(s, red) / (float)n;
+    float q = 0.f;
+    for (int i = tid; i < n; i += NT) {
+      const float t = xi[i] - mean;
+      q = fmaf(t, t, q);
+    }
+    const float rstd = 1.f / sqrtf(block_sum(q, red) / (float)(n - 1) + 1e-5f);
+    __syncthreads();
+    for (int i = tid; i < n; i += NT) xi[i] = fmaf(d.ln_w[i], (xi[i] - mean) * rstd, d.ln_b[i]);
+    __syncthreads();
+    for (int i = tid; i < V * C0; i += NT) {
+      const int v = i / C0, co = i - v * C0;
+      float t = d.b_in[co];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) t = fmaf(d.w_in[co * 3 + c], xi[c * V + v], t);
+      xs[v * ld + co] = t;
+    }
+    __syncthreads();
+  }
+
+  for (int l = 0; l < d.L; ++l) {
+    const stgcn_rt_streams_layer ly = d.layers[l];
+    const int Cin = ly.Cin, Cout = ly.Cout, P = ly.P, ldx = Cin + XPAD;
+    const int E = V * Cout, n4 = E / 4;
+    const int fi = restart ? 0 : ly.idx[b * 2], ai = restart ? 0 : ly.idx[b * 2 + 1];
+    // (1) conv + A-mix per (partition, tile), residual conv per tile
+    {
+      const int ntile = (Cout + 31) / 32, nks = (Cin + 15) / 16, nconv = ntile * P;
+      const int ntask = nconv + (ly.res_mode == 2 ? ntile : 0);
+      const int row = lane & 31, h = lane >> 5;
+      for (int task = w; task < ntask; task += NW) {
+        const bool res = task >= nconv;
+        const int t2 = res ? task - nconv : task;
+        const int p = res ? 0 : t2 / ntile, tile = res ? t2 : t2 - p * ntile;
+        const float* panel = (res ? ly.wrp : ly.wp + (long)p * ntile * nks * 512) + (long)tile * nks * 512;
+        float am[16];  // A_p[u = acc_row(r, lane)][v = row]
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int u = acc_row(r, lane);
+          am[r] = (!res && u < V && row < V) ? ly.A[(p * V + u) * V + row] : 0.f;
+        }
+        f32x16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+        for (int kb = 0; kb < nks; kb += TU) {
+          f32x8 fa[TU], fb[TU];
+#pragma unroll
+          for (int u = 0; u < TU; ++u) fb[u] = load_b<float>(panel, kb + u, nks, lane);
+#pragma unroll
+          for (int u = 0; u < TU; ++u) fa[u] = load_a(xs, ldx, kb + u, nks, row, h, V, Cin);
+#pragma unroll
+          for (int u = 0; u < TU; ++u) Tr<float>::mma(acc, fa[u], fb[u]);
+        }
+        float* dst = rs;
+        if (!res) {
+          f32x16 z;
+#pragma unroll
+          for (int r = 0; r < 16; ++r) z[r] = 0.f;
+#pragma unroll
+          for (int r = 0; r < 16; ++r) z = __builtin_amdgcn_mfma_f32_32x32x2f32(am[r], acc[r], z, 0, 0, 0);
+          acc = z;
+          dst = zs + p * E;
+        }
+        const int co = tile * 32 + row;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int v = acc_row(r, lane);
+          if (v < V && co < Cout) dst[v * Cout + co] = acc[r];
+        }
+      }
+    }
+    __syncthreads();
+    // (2) FIFO step, norms, residual
+    {
+      float* fifo = ly.fifo + (b * ly.fifo_size + fi) * E;
+      float* accu = ly.acc + (b * ly.S + ai) * E;
+      const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+      float4 va[U4], vr[U4];
+#pragma unroll
+      for (int j = 0; j < U4; ++j) {
+        const int e4 = tid + NT * j;
+        va[j] = vr[j] = zero;
+        if (e4 < n4) {
+          float4 s = ly.bias2d ? reinterpret_cast<const float4*>(ly.bias2d)[e4] : zero;
+          for (int p = 0; p < P; ++p) s = add4(s, reinterpret_cast<const float4*>(zs + p * E)[e4]);
+          const float4 oa = restart ? zero : reinterpret_cast<const float4*>(accu)[e4];
+          const float4 of = restart ? zero : reinterpret_cast<const float4*>(fifo)[e4];
+          const float4 a = make_float4(oa.x + s.x - of.x, oa.y + s.y - of.y, oa.z + s.z - of.z, oa.w + s.w - of.w);
+          reinterpret_cast<float4*>(accu)[e4] = a;
+          reinterpret_cast<float4*>(fifo)[e4] = s;
+          va[j] = a;
+          if (ly.res_mode == 1) {
+            const int v = e4 * 4 / Cout, c = e4 * 4 - v * Cout;  // Cin == Cout
+            vr[j] = *reinterpret_cast<const float4*>(xs + v * ldx + c);
+          }
+          if (ly.res_mode == 2) vr[j] = reinterpret_cast<const float4*>(rs)[e4];
+        }
+      }
+      const float2 st = ln_stats_reg(va, n4, red);
+      float2 sr = make_float2(0.f, 1.f);
+      if (ly.res_mode == 2) sr = ln_stats_reg(vr, n4, red);
+      __syncthreads();  // every read of xs (the identity residual) before the overwrite
+      const int ldy = Cout + XPAD;
+#pragma unroll
+      for (int j = 0; j < U4; ++j) {
+        const int e4 = tid + NT * j;
+        if (e4 < n4) {
+          float4 o = relu4(affine4(va[j], st.x, st.y, reinterpret_cast<const float4*>(ly.ln_w)[e4],
+                                   reinterpret_cast<const float4*>(ly.ln_b)[e4]));
+          if (ly.res_mode == 1) o = relu4(add4(o, vr[j]));
+          if (ly.res_mode == 2)
+            o = relu4(add4(o, affine4(vr[j], sr.x, sr.y, reinterpret_cast<const float4*>(ly.lnr_w)[e4],
+                                      reinterpret_cast<const float4*>(ly.lnr_b)[e4])));
+          const int v = e4 * 4 / Cout, c = e4 * 4 - v * Cout;
+          *reinterpret_cast<float4*>(xs + v * ldy + c) = o;
+        }
+      }
+      if (tid == 0) {
+        ly.idx[b * 2] = (fi + 1) % ly.fifo_size;
+        ly.idx[b * 2 + 1] = (ai + 1) % ly.S;
+      }
+      __syncthreads();
+    }
+  }
+
+  // output head (rt_out_kernel's arithmetic)
+  {
+    const int C = d.layers[d.L - 1].Cout, ld = C + XPAD;
+    float* pool = zs;
+    for (int c = tid; c < C; c += NT) {
+      float s = 0.f;
+      for (int v = 0; v < V; ++v) s += xs[v * ld + c];
+      pool[c] = s / (float)V;
+    }
+    __syncthreads();
+    for (int k = w; k < d.K; k += NW) {  // one wave per class, the channels over the lanes
+      float s = 0.f;
+      for (int c = lane; c < C; c += 64) s = fmaf(d.w_out[(long)k * C + c], pool[c], s);
+      s = wave_sum(s);
+      if (lane == 0) out[k] = s + (d.b_out ? d.b_out[k] : 0.f);
+    }
+  }
+}
+
+}  // namespace
+
+int rt_streams_launch(const stgcn_rt_streams_desc& d, hipStream_t s) {
+  if (!d.x || !d.active || !d.ln_w || !d.ln_b || !d.w_in || !d.b_in || !d.w_out || !d.out) return STGCN_EBADSHAPE;
+  if (d.V < 2 || d.V > VMAX || d.L < 1 || d.L > STGCN_RT_MAX_LAYERS || d.C0 < 4 || d.C0 > CMAX || d.C0 % 4 ||
+      d.V * d.C0 > MAXE || d.K < 1 || d.B < 1)
+    return STGCN_EBADSHAPE;
+  int cin = d.C0;
+  for (int l = 0; l < d.L; ++l) {
+    const stgcn_rt_streams_layer& y = d.layers[l];
+    if (y.Cin != cin || y.Cout < 4 || y.Cout > CMAX || y.Cout % 4 || d.V * y.Cout > MAXE || y.P < 1 || y.P > PMAX ||
+        y.fifo_size < 1 || y.S < 1 || y.res_mode < 0 || y.res_mode > 2 || (y.res_mode == 1 && y.Cin != y.Cout))
+      return STGCN_EBADSHAPE;
+    if (!y.A || !y.wp || !y.ln_w || !y.ln_b || !y.fifo || !y.acc || !y.idx ||
+        (y.res_mode == 2 && (!y.wrp || !y.lnr_w || !y.lnr_b)))
+      return STGCN_EBADSHAPE;
+    cin = y.Cout;
+  }
+  constexpr int lds = LDS_FLOATS * (int)sizeof(float);
+  if (stgcn_lds_attr((const void*)rt_streams_kernel, lds, s)) return STGCN_EHIP;
+  hipLaunchKernelGGL(rt_streams_kernel, dim3((unsigned)d.B), dim3(NT), lds, s, d);
+  return hipGetLastError() == hipSuccess ? STGCN_OK : STGCN_EHIP;
+}

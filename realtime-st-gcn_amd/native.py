@@ -1045,6 +1045,29 @@ def rt_frame(desc, x, out):
     return out
 
 
+def rt_streams_pack_weight(w, groups):
+    """``groups`` stacked 1x1-conv weights (groups * rows, Cin) -> rt_streams.hip's MFMA B-fragment image (fp32),
+    one [rows/32 tiles][Cin/16 k-steps][64 lanes][8] panel set per group."""
+    L.require_device(w)
+    w = _f32c(w.detach().reshape(w.shape[0], -1))
+    rows, Cin = w.shape[0] // groups, w.shape[1]
+    n = L.lib().stgcn_rt_streams_pack_elems(rows, Cin)
+    if n < 0 or rows * groups != w.shape[0]:
+        raise RuntimeError(f"stgcn_amd: rt_streams_pack_weight: unsupported shape rows={rows} Cin={Cin}")
+    out = torch.empty(groups * n, dtype=torch.float32, device=w.device)
+    L.check(L.lib().stgcn_rt_streams_pack_weight(w.data_ptr(), groups, rows, Cin, out.data_ptr(), L.stream()),
+            "rt_streams_pack_weight")
+    return out
+
+
+def rt_streams(desc, x, active, out):
+    """One frame of every stream of a stream batch in one launch (stgcn_rt_streams): x (B, 3, 1, V) fp32 dense,
+    active (B) int32, out (B, K, 1); ``desc`` is the batch's stgcn_rt_streams_desc (rtstgcn.RtStreamBatch)."""
+    desc.x, desc.active, desc.out = x.data_ptr(), active.data_ptr(), out.data_ptr()
+    L.check(L.lib().stgcn_rt_streams(ctypes.byref(desc), L.stream()), "rt_streams")
+    return out
+
+
 # ------------------------------------------------------------------------------ CoST-GCN per-frame (co_frame.hip)
 def co_pack_weight(w, dtype):
     """tcn.2 weight (Cout, C, Kt, 1) -> the tap kernel's [tile][k-step][lane][8] image in ``dtype``."""

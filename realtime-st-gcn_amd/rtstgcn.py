@@ -294,15 +294,20 @@ class Model(nn.Module):
         """Key of the frame descriptor: data pointers and in-place versions of every parameter it reads (copies of
         them live in the descriptor), data pointers only of the FIFO state (the kernel updates it in place, and
         reset_state's zeroing must not rebuild the descriptor)."""
-        ts = [self.norm_in.weight, self.norm_in.bias, self.fcn_in.weight, self.fcn_in.bias, self.fcn_out.weight,
-              self.fcn_out.bias]
         st = []
         for l in self.st_gcn:
-            ts += [l.aggregate.A, l.conv.weight, l.conv.bias, l.bn_relu[0].weight, l.bn_relu[0].bias]
             st += [l.aggregate.fifo, l.aggregate.accumulator, l.aggregate.idx]
+        return self._param_key() + tuple(t.data_ptr() for t in st)
+
+    def _param_key(self):
+        """Data pointers and in-place versions of every parameter a per-frame descriptor reads."""
+        ts = [self.norm_in.weight, self.norm_in.bias, self.fcn_in.weight, self.fcn_in.bias, self.fcn_out.weight,
+              self.fcn_out.bias]
+        for l in self.st_gcn:
+            ts += [l.aggregate.A, l.conv.weight, l.conv.bias, l.bn_relu[0].weight, l.bn_relu[0].bias]
             if l.is_residual_conv:
                 ts += [l.residual[0].weight, l.residual[1].weight, l.residual[1].bias]
-        return tuple((t.data_ptr(), t._version) for t in ts) + tuple(t.data_ptr() for t in st)
+        return tuple((t.data_ptr(), t._version) for t in ts)
 
     def _rt_frame(self, x):
         key = self._frame_key()
@@ -356,6 +361,12 @@ class Model(nn.Module):
                 y.r_buf = p(torch.empty(V * Cout, dtype=torch.float32, device=dev))
         return d, keep
 
+    def stream_batch(self, B):
+        """B independent skeleton streams of this online model, advanced together one frame per launch
+        (RtStreamBatch, stgcn_rt_streams).  Valid after prepare_benchmark; the model's own single-stream state and
+        forward are not touched."""
+        return RtStreamBatch(self, B)
+
     def _swap_layers_for_inference(self):
         """Replace OfflineLayers by OnlineLayers carrying the same parameters (rtstgcn.py:160-187)."""
         V = self.A.shape[-1]
@@ -377,3 +388,109 @@ class Model(nn.Module):
         for module in self.st_gcn:
             module.eval_()
         return arch_conf
+
+
+class RtStreamBatch:
+    """B independent skeleton streams of one online LayerNorm rt-st-gcn (Model.stream_batch): every stream has its
+    own FIFO, accumulators and indices for every layer, and ``step`` advances all of them by one frame in one launch
+    (stgcn_rt_streams, rt_streams.hip: one workgroup per stream, no communication between workgroups).  fp32.
+
+    The state buffers live here and survive a rebuild of the descriptor (which follows the parameters' data
+    pointers and in-place versions, as Model._frame_key does); the model's own single-stream state is not used."""
+
+    def __init__(self, model, B):
+        if not model.online:
+            raise RuntimeError("stgcn_amd: stream_batch needs the online layers: call prepare_benchmark first")
+        if model.normalization != "LayerNorm":
+            raise RuntimeError("stgcn_amd: stream_batch supports LayerNorm online models only (BatchNorm online "
+                               "layers are out of scope)")
+        if model.fcn_in.in_channels != 3:
+            raise RuntimeError(f"stgcn_amd: stream_batch needs in_feat == 3, got {model.fcn_in.in_channels}")
+        if int(B) != B or B < 1:
+            raise RuntimeError(f"stgcn_amd: stream_batch needs B >= 1, got {B}")
+        V = model.A.shape[-1]
+        if not model._frame_desc_ok() or V * model.fcn_in.out_channels > 7680:
+            raise RuntimeError("stgcn_amd: stream_batch shape limits: 2 <= V <= 32, channels % 4 == 0 and <= 256, "
+                               f"V * C <= 7680, P <= 3, at most {K.L.RT_MAX_LAYERS} layers")
+        K.L.require_device(model.A)
+        self.model, self.B, self.V = model, int(B), V
+        dev = model.A.device
+        self.state = []  # per layer (fifo [B][fifo][V][C], acc [B][S][V][C], idx [B][2])
+        for l in model.st_gcn:
+            ag = l.aggregate
+            self.state.append((torch.zeros(self.B, ag.fifo_size, V, ag.out_channels, device=dev),
+                               torch.zeros(self.B, ag.stride, V, ag.out_channels, device=dev),
+                               torch.zeros(self.B, 2, dtype=torch.int32, device=dev)))
+        self._all = torch.ones(self.B, dtype=torch.int32, device=dev)
+        self._pack = None
+
+    def _desc(self):
+        m = self.model
+        key = m._param_key()
+        if self._pack is not None and self._pack[0] == key:
+            return self._pack[1]
+        V, keep = self.V, []
+
+        def p(t):
+            keep.append(t)
+            return t.data_ptr()
+
+        d = K.L.RtStreamsDesc()
+        d.V, d.L, d.C0, d.K, d.B = V, len(m.st_gcn), m.fcn_in.out_channels, m.fcn_out.out_channels, self.B
+        d.ln_w, d.ln_b = p(LF._flat_ln(m.norm_in.weight)), p(LF._flat_ln(m.norm_in.bias))
+        d.w_in = p(m.fcn_in.weight.detach().float().reshape(d.C0, -1).contiguous())
+        d.b_in = p(m.fcn_in.bias.detach().float().contiguous())
+        d.w_out = p(m.fcn_out.weight.detach().float().reshape(d.K, -1).contiguous())
+        d.b_out = p(m.fcn_out.bias.detach().float().contiguous())
+        for i, l in enumerate(m.st_gcn):
+            ag = l.aggregate
+            Cin, Cout, P = l.conv.in_channels, ag.out_channels, ag.A.shape[0]
+            A32, _, _, _, bias2d, _ = l._weights(Cin)
+            y = d.layers[i]
+            y.Cin, y.Cout, y.P, y.fifo_size, y.S = Cin, Cout, P, ag.fifo_size, ag.stride
+            y.res_mode = 2 if l.is_residual_conv else (1 if l.is_residual else 0)
+            y.A, y.bias2d = p(A32), p(bias2d)
+            y.wp = p(K.rt_streams_pack_weight(l.conv.weight, P))
+
+            def rows(t):  # LayerNorm([C,1,V]) affine (C,1,V) -> the rows' [V][C] layout
+                return t.detach().float().reshape(Cout, V).t().contiguous()
+
+            n = l.bn_relu[0]
+            y.ln_w, y.ln_b = p(rows(n.weight)), p(rows(n.bias))
+            if l.is_residual_conv:
+                y.wrp = p(K.rt_streams_pack_weight(l.residual[0].weight, 1))
+                y.lnr_w, y.lnr_b = p(rows(l.residual[1].weight)), p(rows(l.residual[1].bias))
+            y.fifo, y.acc, y.idx = (t.data_ptr() for t in self.state[i])
+        self._pack = (key, (d, keep))
+        return self._pack[1]
+
+    def step(self, x, active=None):
+        """x (B, 3, 1, V) -> (B, num_classes, 1).  ``active``: None (every stream steps), an int32 device tensor
+        [B] of codes (0 skip: state untouched, zero output row; 1 step; 2 restart then step) used as given with no
+        host sync, or a bool tensor / Python list converted on the host (True = step)."""
+        B, V = self.B, self.V
+        if x.dim() != 4 or tuple(x.shape) != (B, 3, 1, V):
+            raise RuntimeError(f"stgcn_amd: RtStreamBatch.step expects x of shape {(B, 3, 1, V)}, got {tuple(x.shape)}")
+        K.L.require_device(x)
+        x = K._f32c(x)
+        if active is None:
+            active = self._all
+        elif not (torch.is_tensor(active) and active.dtype == torch.int32 and active.is_cuda):
+            active = torch.as_tensor(active).to(device=x.device, dtype=torch.int32)
+        if tuple(active.shape) != (B,) or not active.is_contiguous():
+            raise RuntimeError(f"stgcn_amd: RtStreamBatch.step expects active of shape ({B},)")
+        d, _keep = self._desc()
+        out = torch.empty((B, d.K, 1), dtype=torch.float32, device=x.device)
+        return K.rt_streams(d, x, active, out)
+
+    def reset(self, streams=None):
+        """Zero the FIFO state of the given streams (an iterable of stream indices), or of all of them."""
+        if streams is None:
+            for ts in self.state:
+                for t in ts:
+                    t.zero_()
+            return
+        idx = torch.as_tensor(list(streams), dtype=torch.long, device=self.state[0][0].device)
+        for ts in self.state:
+            for t in ts:
+                t.index_fill_(0, idx, 0)

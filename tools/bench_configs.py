@@ -23,7 +23,12 @@ ms:       MS-TCN refinement stage (F = 64, 10 layers, 52 classes, L = 2000; ms_s
           refinement stages; LossMultiStage, backward, Adam).  The plain-PyTorch restatement of the stage
           (tests/mstcn_ref.py) is timed on the host beside it.  Only with --only ms.
 
-    python tools/bench_configs.py [--frames 2000] [--steps 10] [--only 3|5|ln|f1|co|ms]
+streams:  config 3 as a stream batch (Model.stream_batch, stgcn_rt_streams): B in {1, 8, 64, 256, 1024} streams
+          advanced one frame per launch, HIP-event device time over 200 graph-replayed ticks after the FIFOs have
+          filled, beside the single-stream one-launch route (stgcn_rt_frame) graph-replayed in the same run: ms per
+          tick, frames/s, and the ratio against B sequential single-stream replays.  Only with --only streams.
+
+    python tools/bench_configs.py [--frames 2000] [--steps 10] [--only 3|5|ln|f1|co|ms|streams]
 Prints one JSON line per config.
 """
 import argparse
@@ -157,6 +162,57 @@ def _config3_route(m, stream, frames):
         torch.cuda.synchronize()
         out["graph"]["device_ms_per_frame"] = round(e0.elapsed_time(e1) / 200, 4)
     return out
+
+
+def _replay_ms(step, fill, reps=200):
+    """Device ms per replay of ``step`` captured as a HIP graph: ``fill`` replays first (the FIFOs fill), then HIP
+    events around ``reps`` back-to-back replays."""
+    step()  # descriptor, weight packs and launch attributes outside the capture
+    g = torch.cuda.CUDAGraph()
+    s_ = torch.cuda.Stream()
+    s_.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s_):
+        with torch.cuda.graph(g):
+            step()
+    torch.cuda.current_stream().wait_stream(s_)
+    for _ in range(fill):
+        g.replay()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        g.replay()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+def streams(P, dev, batches=(1, 8, 64, 256, 1024)):
+    torch.manual_seed(0)
+    m = P.MODELS["rt-st-gcn"](rank=None, **dict(RT_ARCH, graph=P.PKU_MMD)).to(dev)
+    m.eval()
+    m.prepare_benchmark(RT_ARCH)
+    gen = torch.Generator(device=dev).manual_seed(3)
+    fill = 32  # > the 17-frame FIFO of the stride-2 layers
+    R = P.routing.ROUTING
+    prev = R.rt_one_launch
+    rows = []
+    with torch.no_grad():
+        try:
+            R.rt_one_launch = True
+            x1 = torch.randn(1, 3, 1, 25, device=dev, generator=gen)
+            single = _replay_ms(lambda: m(x1), fill)
+        finally:
+            R.rt_one_launch = prev
+        for B in batches:
+            sb = m.stream_batch(B)
+            x = torch.randn(B, 3, 1, 25, device=dev, generator=gen)
+            ms = _replay_ms(lambda: sb.step(x), fill)
+            rows.append({"config": "3 as a stream batch (stgcn_rt_streams): B streams, one frame each per launch",
+                         "dtype": "fp32", "B": B, "tick_device_ms": round(ms, 4),
+                         "frames_per_s": round(B / ms * 1e3, 1),
+                         "single_stream_one_launch_device_ms": round(single, 4),
+                         "ratio_vs_B_sequential": round(ms / (B * single), 4)})
+    return rows
 
 
 def config5(P, dev, steps, warmup):
@@ -490,6 +546,9 @@ def main():
             print(json.dumps(ms_stage(P, dev, dtype)), flush=True)
         for dtype in ("fp32", "bf16"):
             print(json.dumps(msgcn_step(P, dev, dtype, min(args.steps, 5))), flush=True)
+    if args.only == "streams":
+        for row in streams(P, dev):
+            print(json.dumps(row), flush=True)
     if args.only == "co":
         for kernel in (9, 69):
             for dtype in ("fp32", "bf16"):
