@@ -9,20 +9,36 @@ StgcnLayer.forward (models/stgcn/stgcn.py:181-193) is
 
 with norm = BatchNorm2d(track_running_stats=False) or the custom LayerNorm([C,1,V]).
 
-Kernel schedule (forward, BatchNorm):
-  amix_fwd(x, A)                -> XA                     (A applied first, exact)
-  gcn_bias(A, b)                -> bias2d[V][C]
-  conv_rows(XA, Wg, bias2d)     -> g   + BN1 partial stats (epilogue)
+Host path.  A module builds one LayerCfg (RtLayerCfg for the rt-st-gcn offline layer) by keyword per call and
+passes it to the Function as its one non-tensor argument; forward keeps its tensors with _save_named (all through
+ctx.save_for_backward, None allowed) and backward reads them back by name with _saved.
+
+Kernel schedule (forward, BatchNorm), graph conv by route:
+  gathered (batch-shared sparse A with bound support lists; the model's layers):
+    gconv_weights(A, Wg, b)       -> per-joint effective weights + bias2d[V][C]   (or the model's PrepPlan packs)
+    gconv(x, Weff, bias2d)        -> g   + BN1 partial stats (epilogue); no XA in HBM
+  A-first (per-sample 4-D A, dense support, bare ConvTemporalGraphical, rt-st-gcn offline): gcn_forward
+    amix_fwd(x, A)                -> XA                     (A applied first, exact)
+    gcn_bias(A, b)                -> bias2d[V][C]
+    conv_rows(XA, Wg, bias2d)     -> g   + BN1 partial stats (epilogue)
+  then
   bn_finalize                   -> scale1/shift1
   conv_rows(g, Wt, pro=BN1+ReLU)-> u   + BN2 partial stats (prologue applies norm1+ReLU on load)
   [conv_rows(x, Wr, s) -> r + stats ; finalize]
   bn_finalize, bn_apply(u, +res, ReLU) -> y
-Backward mirrors it with the transposed convs (conv_rows trans=1), the m-reduction weight-grad
-kernel (conv_wgrad), the BN reduce/apply pair, amix_trans / amix_dA for the graph part.
-Everything is a HIP kernel of libstgcn_amd.so; the only torch work here is allocation, weight
-re-packing (tiny tensors) and the (P x V)-sized reshuffles of the A/bias gradients.
+LayerNorm: ln_stats / ln_apply in place of the BN pairs (h = relu(LN1(g)) materialised), or for a bf16 64 -> 64
+stride-1 layer the whole forward as one kernel (fused_layer_forward).
+Backward mirrors it: the fused BN reduce/apply pair (bn_bwd_fused) or _norm_backward, the transposed convs
+(conv_rows trans=1 / tconv_frame), the weight-gradient kernels (conv_wgrad_w), and for the graph part gconv
+trans + gconv_wgrad + finish (gathered) or gcn_backward (A-first: amix_trans / amix_dA / conv_wgrad and the bias
+pushed through A by _bias_through_A).  gcn_forward / gcn_backward are the only A-first implementation.
+Everything is a HIP kernel of libstgcn_amd.so; the only torch work here is allocation, weight re-packing (tiny
+tensors) and, for a per-sample A only, the (P x V)-sized einsums of the A/bias gradients.
 """
 from __future__ import annotations
+
+from types import SimpleNamespace
+from typing import NamedTuple
 
 import torch
 
@@ -32,20 +48,73 @@ from .syncbn import active_sync
 
 BN, LN = "BatchNorm", "LayerNorm"
 
+
+class LayerCfg(NamedTuple):
+    """StgcnLayerFunction's non-tensor argument, built by keyword once per layer call."""
+    kt: int
+    stride: int
+    residual: bool
+    norm: str
+    dtype: torch.dtype
+    sup: object = None       # native.GraphSupport of the bound graph (None: per-sample A, the A-first route)
+    dense_dA: bool = False   # caller-owned A: its gradient is wanted off the support too
+    infer: bool = False      # no autograd graph will be built: the one-kernel forward may run
+    cache: dict = None       # the layer's pack / statistics-arena cache
+    packs: object = None     # LayerPacks of the model's PrepPlan launch
+    sync: object = None      # syncbn.BnSync of a SyncBatchNorm run
+
+
+class RtLayerCfg(NamedTuple):
+    """RtOfflineLayerFunction's non-tensor argument."""
+    Kt: int
+    S: int
+    residual: bool
+    norm: str
+    dtype: torch.dtype
+    sync: object = None
+
+
+def _save_named(ctx, **tensors):
+    """save_for_backward under names: every value (a tensor or None) goes through ctx.save_for_backward, so
+    version-counter checks and lifetime are autograd's; only the names are kept on ctx."""
+    ctx.saved_names = tuple(tensors)
+    ctx.save_for_backward(*tensors.values())
+
+
+def _saved(ctx):
+    """What _save_named kept, attribute-addressable."""
+    return SimpleNamespace(**dict(zip(ctx.saved_names, ctx.saved_tensors)))
+
+
+def _f32(p):
+    """Detached fp32 contiguous form of a parameter or adjacency (what the kernels read)."""
+    return p.detach().float().contiguous()
+
+
 def _flat_ln(p):
     """LayerNorm([C,1,V]) parameter (C,1,V) -> flat fp32 [C*V] indexed c*V+v (kernel convention)."""
     return p.detach().reshape(-1).float().contiguous()
 
 
+def _wg_rows(wg, P, Cout, Cin):
+    """Graph-conv weight (P*Cout, Cin, 1, 1) as the A-first GEMM's rows [1][Cout][P*Cin]."""
+    return wg.detach().float().view(P, Cout, Cin).permute(1, 0, 2).reshape(1, Cout, P * Cin)
+
+
+def _wg_rows_T(wg, P, Cout, Cin):
+    """The transposed form [1][P*Cin][Cout] (data gradient)."""
+    return wg.detach().float().view(P, Cout, Cin).permute(0, 2, 1).reshape(1, P * Cin, Cout)
+
+
 def gcn_forward(x, A32, wg, bg, dtype, stats=None):
-    """ConvTemporalGraphical forward on rows: XA = A-mix(x); g = XA @ Wg' + bias2d.  Returns (XA, g, cp)."""
+    """ConvTemporalGraphical forward on rows: XA = A-mix(x); g = XA @ Wg' + bias2d (+ BatchNorm partial statistics
+    into ``stats`` from the same epilogue).  Returns (XA, g, cp)."""
     N, Cin, T, V = x.shape
     P = A32.shape[-3]
     Cout = wg.shape[0] // P
     XA = K.amix_fwd(x, A32)
-    wg3 = wg.detach().float().view(P, Cout, Cin).permute(1, 0, 2).reshape(1, Cout, P * Cin)
-    wgp, cp, kp = K.pack_weight(wg3, dtype)
-    bias2d = K.gcn_bias(A32, bg.detach().float().contiguous(), N, Cout)
+    wgp, cp, kp = K.pack_weight(_wg_rows(wg, P, Cout, Cin), dtype)
+    bias2d = K.gcn_bias(A32, _f32(bg), N, Cout)
     g = K.conv_rows(XA, wgp, P * Cin, Cout, cp, kp, T, T, bias=bias2d, bias_mode=3 if A32.dim() == 4 else 2,
                     stats=stats)
     return XA, g, cp
@@ -56,30 +125,43 @@ def gcn_stats_buffer(M, Cout, dev):
     return torch.zeros((K.row_blocks(M, Cout), cp, 4), dtype=torch.float32, device=dev), cp
 
 
-def gcn_backward(x, A32, XA, wg, bg, dg, dx, accumulate, dtype):
-    """Backward of gcn_forward given dg: dx (+)= A^T-mix(dg @ Wg), returns (dA fp32, dWg, dbg)."""
+def _gcn_dgrad_rows(dg, wg, P, Cin, Cout, T, dtype):
+    """DW[(n,t,w)][p*Cin+ci] = sum_c dg[(n,t,w)][c] Wg[p*Cout+c][ci]: dg through the transposed 1x1 weights."""
+    wgTp, cq, kq = K.pack_weight(_wg_rows_T(wg, P, Cout, Cin), dtype)
+    return K.conv_rows(dg, wgTp, Cout, P * Cin, cq, kq, T, T)
+
+
+def gcn_backward(x, A32, XA, wg, bg, dg, dx, accumulate, dtype, z_S=None):
+    """Backward of gcn_forward given dg: dx (+)= A^T-mix(dg @ Wg), returns (dA fp32, dWg, dbg).  ``z_S``: a zeroed
+    buffer for the per-joint row sums of dg (_bias_through_A), else allocated."""
     N, Cin, T, V = x.shape
     P = A32.shape[-3]
     Cout = wg.shape[0] // P
-    M = N * T * V
-    wgT = wg.detach().float().view(P, Cout, Cin).permute(0, 2, 1).reshape(1, P * Cin, Cout)
-    wgTp, cq, kq = K.pack_weight(wgT, dtype)
-    DW = K.conv_rows(dg, wgTp, Cout, P * Cin, cq, kq, T, T)
+    DW = _gcn_dgrad_rows(dg, wg, P, Cin, Cout, T, dtype)
     K.amix_trans(DW, A32, Cin, dx, accumulate=accumulate)
     dA = K.amix_dA(x, DW, A32)
-    bgp = bg.detach().float().view(P, Cout)
-    # the conv bias pushed through A: dA[p][v][w] += sum_c b_p[c] S[w][c] (independent of v)
-    if A32.dim() == 4:
-        Sn = K.rowgroup_sum(dg, M, Cout, V, per_sample=True)            # [N][V(w)][Cout]
-        dA += torch.einsum("pc,nwc->npw", bgp, Sn).unsqueeze(2)
-        dbg = torch.einsum("npw,nwc->pc", A32.sum(dim=2), Sn).reshape(-1)
-    else:
-        S = K.rowgroup_sum(dg, M, Cout, V)                               # [V(w)][Cout]
-        dA += (bgp @ S.t()).unsqueeze(1)
-        dbg = (A32.sum(dim=1) @ S).reshape(-1)
     dwg = K.conv_wgrad(XA, dg, P * Cin, Cout, T, T, Kt=1)                # [1][Cout][P*Cin]
     dwg = dwg.view(Cout, P, Cin).permute(1, 0, 2).reshape(P * Cout, Cin, 1, 1)
+    dA, dbg = _bias_through_A(dA, A32, bg, dg, z_S=z_S)
     return dA, dwg, dbg
+
+
+def _bias_through_A(dA, A32, bg, dg, S=None, z_S=None):
+    """The conv bias pushed through A: dA[p][v][w] += sum_c b_p[c] S[w][c] (independent of v), S = per-joint row
+    sums of dg (``S``: already produced by the joint-grouped weight-gradient kernel; else summed here, into the
+    zeroed ``z_S`` when given).  Returns (dA, dbg)."""
+    N, Cout, T, V = dg.shape
+    M = N * T * V
+    if A32.dim() == 4:
+        Sn = K.rowgroup_sum(dg, M, Cout, V, per_sample=True, out=z_S)   # [N][V(w)][Cout]
+        dA = dA + torch.einsum("pc,nwc->npw", bg.detach().float().view(-1, Cout), Sn).unsqueeze(2)
+        colsum = A32.sum(dim=2)                                         # [N][P][W]
+        return dA, torch.einsum("npw,nwc->pc", colsum, Sn).reshape(-1)
+    if S is None:
+        S = K.rowgroup_sum(dg, M, Cout, V, out=z_S)                     # [V(w)][Cout]
+    if not dA.is_contiguous():
+        dA = dA.contiguous()
+    return dA, K.gcn_bias_bwd(A32, _f32(bg), S, dA, Cout)
 
 
 def _packs(cache, wg, wt, P, Cin, Cout, dtype):
@@ -88,8 +170,7 @@ def _packs(cache, wg, wt, P, Cin, Cout, dtype):
     key = (wg.data_ptr(), wg._version, wt.data_ptr(), wt._version, dtype)
     if cache is not None and cache.get("key") == key:
         return cache["val"]
-    wgf = wg.detach().float().view(P, Cout, Cin).permute(1, 0, 2).reshape(Cout, P * Cin)
-    wimg, cpg, kwg = K.pack_gcn_weight(wgf, dtype)
+    wimg, cpg, kwg = K.pack_gcn_weight(_wg_rows(wg, P, Cout, Cin)[0], dtype)
     wt3 = wt.detach().float().squeeze(-1).permute(2, 0, 1)  # [Kt][Cout][Cin]
     wtp, _, _ = K.pack_weight(wt3, dtype, stride=1)
     val = (wimg, cpg, kwg, wtp)
@@ -146,11 +227,10 @@ def fused_layer_forward(x, A32, wg, bg, n1w, n1b, wt, bt, n2w, n2b, residual, dt
     Cout = wt.shape[0]
     if packs is not None and packs.wt is not None and packs.gw is not None:
         bias2d = packs.gw[1]
-        wgf = wg.detach().float().view(P, Cout, Cin).permute(1, 0, 2).reshape(Cout, P * Cin)
-        wimg, cpg, kwg = K.pack_gcn_weight(wgf, dtype)
+        wimg, cpg, kwg = K.pack_gcn_weight(_wg_rows(wg, P, Cout, Cin)[0], dtype)
         wtp = packs.wt[0]
     else:
-        bias2d = K.gcn_bias(A32, bg.detach().float().contiguous(), N, Cout)
+        bias2d = K.gcn_bias(A32, _f32(bg), N, Cout)
         wimg, cpg, kwg, wtp = _packs(cache, wg, wt, P, Cin, Cout, dtype)
     # the LayerNorm([64,1,V]) parameters as per-joint [V][64] rows, re-laid-out when one changed (every training
     # step): one stacking launch for the four (the kernel reads 16-B channel runs per joint)
@@ -161,8 +241,7 @@ def fused_layer_forward(x, A32, wg, bg, n1w, n1b, wt, bt, n2w, n2b, residual, dt
         ln = tuple(torch.stack([p.detach().float().reshape(Cout, V).t() for p in (n1w, n1b, n2w, n2b)]).unbind(0))
         if cache is not None:
             cache["ln_key"], cache["ln_val"] = lkey, ln
-    return K.layer_fused(x, A32, wimg, bias2d, wtp, bt.detach().float().contiguous(), ln, tag=tag, residual=residual,
-                         train=train)
+    return K.layer_fused(x, A32, wimg, bias2d, wtp, _f32(bt), ln, tag=tag, residual=residual, train=train)
 
 
 def _stats_arena(cache, dev, dtype, shapes, route):
@@ -191,7 +270,8 @@ class StgcnLayerFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, A, wg, bg, n1w, n1b, wt, bt, n2w, n2b, wr, br, nrw, nrb, cfg):
-        kt, stride, residual, norm, dtype = cfg[:5]
+        kt, stride, residual, norm, dtype, sup, packs = (cfg.kt, cfg.stride, cfg.residual, cfg.norm, cfg.dtype,
+                                                         cfg.sup, cfg.packs)
         dev = x.device
         x = K.to_rows(x, dtype)
         N, Cin, T, V = x.shape
@@ -200,26 +280,23 @@ class StgcnLayerFunction(torch.autograd.Function):
         pad = (kt - 1) // 2
         T_out = (T + 2 * pad - kt) // stride + 1
         M1, M2 = N * T * V, N * T_out * V
-        A32 = A.detach().float().contiguous()
+        A32 = _f32(A)
         res_conv = residual and not (Cin == Cout and stride == 1)
-        packs = cfg[9] if len(cfg) > 9 else None  # LayerPacks of the model's PrepPlan launch, or None
         # the layer's cache, one sub-dict per device: DataParallel replicas share the module's dict (shallow
         # __dict__ copy) and run in one thread per device, so each thread only ever touches its own sub-dict
         # (dict.setdefault is atomic under the GIL)
-        cache = cfg[8].setdefault(("dev", str(dev)), {}) if len(cfg) > 8 and cfg[8] is not None else None
+        cache = cfg.cache.setdefault(("dev", str(dev)), {}) if cfg.cache is not None else None
         # SyncBatchNorm (syncbn.py): the statistics of every rank, else this rank's (the reference's DataParallel)
-        sync = cfg[10] if len(cfg) > 10 else None
-        bn_finalize = sync.finalize if sync is not None else K.bn_finalize
+        bn_finalize = cfg.sync.finalize if cfg.sync is not None else K.bn_finalize
 
         # ---- graph convolution: g = sum_p A_p-mix(x) W_p + bias2d
-        sup = cfg[5] if len(cfg) > 5 else None
         gather = sup is not None and A32.dim() == 3 and not sup.dense(P)
-        if (gather and len(cfg) > 7 and cfg[7] and ROUTING.fused_inference and norm == LN
+        if (gather and cfg.infer and ROUTING.fused_inference and norm == LN
                 and K.layer_fused_ok(sup, P, Cin, Cout, V, kt, stride, dtype)):
             # inference of a LayerNorm 64 -> 64 stride-1 layer: the one-kernel layer (g never leaves the chip;
             # nothing saved for backward): 0.12 vs 0.15-0.21 ms unfused
             return fused_layer_forward(x, A32, wg, bg, n1w, n1b, wt, bt, n2w, n2b, residual, dtype, cache=cache)
-        if (gather and norm == LN and ROUTING.fused_ln_train and not (len(cfg) > 7 and cfg[7])
+        if (gather and norm == LN and ROUTING.fused_ln_train and not cfg.infer
                 and K.layer_fused_ok(sup, P, Cin, Cout, V, kt, stride, dtype)):
             # training forward of a LayerNorm 64 -> 64 stride-1 layer: the one-kernel layer (g and h on chip for
             # the temporal conv) also writes g, u and both LN statistics — exactly what the unfused forward
@@ -229,12 +306,11 @@ class StgcnLayerFunction(torch.autograd.Function):
             ctx.cfg = cfg
             ctx.sup = sup
             ctx.dims = (N, Cin, Cout, T, T_out, V, P, pad, False)
-            ctx.packs = None
-            ctx.save_for_backward(x, A32, None, g, u, y, wg, bg, wt, n1w, n1b, n2w, n2b, ls1, ls2, h)
+            _save_named(ctx, x=x, A32=A32, XA=None, g=g, u=u, y=y, wg=wg, bg=bg, wt=wt, n1w=n1w, n1b=n1b, n2w=n2w,
+                        n2b=n2b, ls1=ls1, ls2=ls2, h=h)
             ctx.in_dtype = A.dtype
             return y
-        # gathered path: bias2d comes from the weight preparation below
-        bias2d = None if gather else K.gcn_bias(A32, bg.detach().float().contiguous(), N, Cout)
+        st1 = st2 = str_ = None
         if norm == BN:  # all BatchNorm partial-statistics buffers of the layer from one zero fill
             cpo = -(-Cout // K.col_tile(Cout)) * K.col_tile(Cout)
             rb1 = K.gconv_row_blocks(N * T, V) if gather else K.row_blocks(M1, Cout)
@@ -246,36 +322,29 @@ class StgcnLayerFunction(torch.autograd.Function):
         # ---- residual branch: independent of the graph conv -> temporal conv chain until the output norm
         r = None
         if res_conv:
-            wrp, cpr, kpr = packs.wr if packs is not None else \
-                K.pack_weight(wr.detach().float().view(1, Cout, Cin), dtype)
-            r = K.conv_rows(x, wrp, Cin, Cout, cpr, kpr, T, T_out, Kt=1, stride=stride, pad=0,
-                            bias=br.detach().float().contiguous(), stats=str_ if norm == BN else None)
+            wrp, cpr, kpr = packs.wr if packs is not None else K.pack_weight(_f32(wr).view(1, Cout, Cin), dtype)
+            r = K.conv_rows(x, wrp, Cin, Cout, cpr, kpr, T, T_out, Kt=1, stride=stride, pad=0, bias=_f32(br),
+                            stats=str_)
             if norm == BN:
-                mrr, scr, shr = bn_finalize(str_, str_.shape[0], cpr, Cout, nrw.detach().float(), nrb.detach().float())
+                strr, scr, shr = bn_finalize(str_, str_.shape[0], cpr, Cout, _f32(nrw), _f32(nrb))
             else:
-                lsr = K.ln_stats(r, N * T_out, V, Cout)
+                strr = K.ln_stats(r, N * T_out, V, Cout)
 
         if gather:  # joint-gathered GEMM over per-joint effective weights (gconv.hip), no XA in HBM
             if packs is not None and packs.gw is not None:
                 wgp, bias2d = packs.gw
             else:
-                wg2 = wg.detach().float().reshape(P * Cout, Cin).contiguous()
-                wgp, bias2d = K.gconv_weights(A32, wg2, sup, Cout, Cin, False, dtype,
-                                              bias=bg.detach().float().contiguous())
-            cpg, kpg = wgp.shape[2], wgp.shape[3]
+                wgp, bias2d = K.gconv_weights(A32, _f32(wg).reshape(P * Cout, Cin), sup, Cout, Cin, False, dtype,
+                                              bias=_f32(bg))
+            cpg = wgp.shape[2]
             if norm == BN:
                 assert cpg == cpo
-            g = K.gconv(x, wgp, sup, Cin, Cout, bias=bias2d, stats=st1 if norm == BN else None)
+            g = K.gconv(x, wgp, sup, Cin, Cout, bias=bias2d, stats=st1)
             XA = None
-        else:
-            XA = K.amix_fwd(x, A32)
-            wg3 = wg.detach().float().view(P, Cout, Cin).permute(1, 0, 2).reshape(1, Cout, P * Cin)
-            wgp, cpg, kpg = K.pack_weight(wg3, dtype)
-            bmode = 3 if A32.dim() == 4 else 2
-            g = K.conv_rows(XA, wgp, P * Cin, Cout, cpg, kpg, T, T, bias=bias2d, bias_mode=bmode,
-                            stats=st1 if norm == BN else None)
+        else:  # per-sample or dense A: A-mix first, BN1 partials from the same GEMM epilogue
+            XA, g, cpg = gcn_forward(x, A32, wg, bg, dtype, stats=st1)
         if norm == BN:
-            mr1, sc1, sh1 = bn_finalize(st1, st1.shape[0], cpg, Cout, n1w.detach().float(), n1b.detach().float())
+            mr1, sc1, sh1 = bn_finalize(st1, st1.shape[0], cpg, Cout, _f32(n1w), _f32(n1b))
             pro1 = dict(pro=1, pro_a=sc1, pro_b=sh1)
         else:
             # LayerNorm: h = relu(LN1(g)) is materialised (one HBM-bound pass, ln.hip) and the temporal conv runs
@@ -290,12 +359,11 @@ class StgcnLayerFunction(torch.autograd.Function):
         wtp, cpt, kpt = packs.wt if packs is not None else \
             K.pack_weight(wt.detach().float().squeeze(-1).permute(2, 0, 1), dtype, stride=stride)  # [Kt][Cout][Cin]
         u = K.conv_rows(g if norm == BN else h, wtp, Cout, Cout, cpt, kpt, T, T_out, Kt=kt, stride=stride,
-                        pad=pad, bias=bt.detach().float().contiguous(), stats=st2 if norm == BN else None,
-                        tag=f"tcn_fwd_c{Cout}" if stride == 1 else None, **pro1)
+                        pad=pad, bias=_f32(bt), stats=st2, tag=f"tcn_fwd_c{Cout}" if stride == 1 else None, **pro1)
 
         # ---- y = relu(norm2(u) + res)
         if norm == BN:
-            mr2, sc2, sh2 = bn_finalize(st2, st2.shape[0], cpt, Cout, n2w.detach().float(), n2b.detach().float())
+            mr2, sc2, sh2 = bn_finalize(st2, st2.shape[0], cpt, Cout, _f32(n2w), _f32(n2b))
             # the output's sign bits for the backward's ReLU mask (the fused BN backward reads them instead of y:
             # 1/16 of the bytes in both of its passes)
             ybits = torch.empty((M2, Cout // 8), dtype=torch.uint8, device=dev) \
@@ -310,7 +378,7 @@ class StgcnLayerFunction(torch.autograd.Function):
             ls2 = K.ln_stats(u, N * T_out, V, Cout)
             g2, b2 = _flat_ln(n2w), _flat_ln(n2b)
             if res_conv:
-                y = K.ln_apply(u, ls2, g2, b2, M2, V, Cout, res_mode=2, r=r, rst=lsr, rg=_flat_ln(nrw),
+                y = K.ln_apply(u, ls2, g2, b2, M2, V, Cout, res_mode=2, r=r, rst=strr, rg=_flat_ln(nrw),
                                rb=_flat_ln(nrb))
             else:
                 y = K.ln_apply(u, ls2, g2, b2, M2, V, Cout, res_mode=1 if residual else 0,
@@ -319,39 +387,30 @@ class StgcnLayerFunction(torch.autograd.Function):
         ctx.cfg = cfg
         ctx.sup = sup if gather else None
         ctx.dims = (N, Cin, Cout, T, T_out, V, P, pad, res_conv)
-        ctx.packs = (cpg, kpg, cpt, kpt)
-        saved = [x, A32, XA, g, u, y, wg, bg, wt, n1w, n1b, n2w, n2b]
+        saved = dict(x=x, A32=A32, XA=XA, g=g, u=u, y=y, wg=wg, bg=bg, wt=wt, n1w=n1w, n1b=n1b, n2w=n2w, n2b=n2b)
         if norm == BN:
-            saved += [mr1, sc1, sh1, mr2, ybits]
+            saved.update(mr1=mr1, sc1=sc1, sh1=sh1, mr2=mr2, ybits=ybits)
         else:
-            saved += [ls1, ls2, h]
-        if res_conv:
-            saved += [r, wr, nrw, nrb] + ([mrr] if norm == BN else [lsr])
-        ctx.save_for_backward(*saved)
+            saved.update(ls1=ls1, ls2=ls2, h=h)
+        if res_conv:  # strr: the residual norm's (mean, rstd), BatchNorm per channel / LayerNorm per frame
+            saved.update(r=r, wr=wr, nrw=nrw, nrb=nrb, strr=strr)
+        _save_named(ctx, **saved)
         ctx.in_dtype = A.dtype
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        kt, stride, residual, norm, dtype = ctx.cfg[:5]
+        cfg, s = ctx.cfg, _saved(ctx)
+        kt, stride, residual, norm, dtype, packs, sync = (cfg.kt, cfg.stride, cfg.residual, cfg.norm, cfg.dtype,
+                                                          cfg.packs, cfg.sync)
         N, Cin, Cout, T, T_out, V, P, pad, res_conv = ctx.dims
-        sv = list(ctx.saved_tensors)
-        x, A32, XA, g, u, y, wg, bg, wt, n1w, n1b, n2w, n2b = sv[:13]
-        rest = sv[13:]
-        ybits = None
-        if norm == BN:
-            mr1, sc1, sh1, mr2, ybits = rest[:5]
-            rest = rest[5:]
-        else:
-            ls1, ls2, h = rest[:3]
-            rest = rest[3:]
-        if res_conv:
-            r, wr, nrw, nrb, strr = rest
+        x, A32, g, u, y, wg, bg, wt = s.x, s.A32, s.g, s.u, s.y, s.wg, s.bg, s.wt
+        # (mean, rstd) of norm1 / norm2: BatchNorm per channel, LayerNorm per frame
+        st1, st2 = (s.mr1, s.mr2) if norm == BN else (s.ls1, s.ls2)
+        ybits = s.ybits if norm == BN else None
         dev = x.device
         dy = K.to_rows(dy, dtype)
         M1, M2 = N * T * V, N * T_out * V
-        packs = ctx.cfg[9] if len(ctx.cfg) > 9 else None
-        sync = ctx.cfg[10] if len(ctx.cfg) > 10 else None
         grads = {}
         # the temporal / residual weight gradients come back in nn.Conv2d order, overwritten (conv_wgrad_w); the
         # graph-conv accumulation targets (dW, dA, per-joint row sums) are zero-filled only on the routes that
@@ -372,56 +431,36 @@ class StgcnLayerFunction(torch.autograd.Function):
         # identity residual with the forward's sign bits and the gathered graph conv: its masked gradient
         # dy * [y > 0] is added in the graph conv's data-gradient epilogue (not written to dx by the BN backward)
         res_in_gconv = fused and residual and not res_conv and ybits is not None and ctx.sup is not None
-        bt_done = False
         if fused:
             # one reduce + one apply pass: du, the residual branch's dr (or dx = dz), and the conv-bias
             # gradients (column sums of du / dr) together
-            kw = dict(mask=1, mref=y, x1=u, mr1=mr2, g1=n2w.detach().float(), out1=du, bias_sums=True)
+            kw = dict(mask=1, mref=y, x1=u, mr1=st2, g1=_f32(s.n2w), out1=du, bias_sums=True)
             if ybits is not None:
                 kw.update(mask=3, mref=ybits)
             if res_conv:
                 dr = K.cl_empty(N, Cout, T_out, V, dtype, dev)
-                kw.update(x2=r, mr2=strr, g2=nrw.detach().float(), out2=dr)
+                kw.update(x2=s.r, mr2=s.strr, g2=_f32(s.nrw), out2=dr)
             elif residual and not res_in_gconv:
                 kw.update(out2=dx)
                 dx_written = True
             sums2, osum2 = K.bn_bwd_fused(dy, M2, Cout, sync=sync, **kw)
             grads["n2w"], grads["n2b"] = sums2[1], sums2[0]
             grads["bt"] = osum2[0]
-            bt_done = True
             if res_conv:  # nrb == n2b numerically; own storage so no two parameters share a grad tensor
                 grads["nrw"], grads["nrb"] = sums2[2], sums2[0].clone()
                 grads["br"] = osum2[1]
-        elif norm == BN:
-            s2 = K.bn_bwd_reduce(dy, M2, Cout, mask=1, mref=y, x=u, mean_rstd=mr2)
-            grads["n2w"], grads["n2b"] = s2[:, 1].clone(), s2[:, 0].clone()
-            if sync is not None:
-                sync.all_reduce_sums(s2, M2)
-            K.bn_bwd_apply(dy, M2, Cout, du, mask=1, mref=y, x=u, mean_rstd=mr2, gamma=n2w.detach().float(), sums=s2)
         else:
-            dgb2 = torch.zeros((2, Cout * V), dtype=torch.float32, device=dev)
-            K.ln_bwd(dy, u, ls2, _flat_ln(n2w), _flat_ln(n2b), N * T_out, V, Cout, du, mask=1, mref=y, dgb=dgb2)
-            grads["n2w"], grads["n2b"] = dgb2[0].view(n2w.shape), dgb2[1].view(n2b.shape)
+            grads["n2w"], grads["n2b"] = _norm_backward(norm, dy, u, st2, s.n2w, s.n2b, du, sync, mask=1, mref=y)
 
         if res_conv:
             if not fused:
                 dr = K.cl_empty(N, Cout, T_out, V, dtype, dev)
-                if norm == BN:
-                    sr = K.bn_bwd_reduce(dy, M2, Cout, mask=1, mref=y, x=r, mean_rstd=strr)
-                    grads["nrw"], grads["nrb"] = sr[:, 1].clone(), sr[:, 0].clone()
-                    if sync is not None:
-                        sync.all_reduce_sums(sr, M2)
-                    K.bn_bwd_apply(dy, M2, Cout, dr, mask=1, mref=y, x=r, mean_rstd=strr,
-                                   gamma=nrw.detach().float(), sums=sr)
-                else:
-                    dgbr = torch.zeros((2, Cout * V), dtype=torch.float32, device=dev)
-                    K.ln_bwd(dy, r, strr, _flat_ln(nrw), _flat_ln(nrb), N * T_out, V, Cout, dr, mask=1, mref=y,
-                             dgb=dgbr)
-                    grads["nrw"], grads["nrb"] = dgbr[0].view(nrw.shape), dgbr[1].view(nrb.shape)
+                grads["nrw"], grads["nrb"] = _norm_backward(norm, dy, s.r, s.strr, s.nrw, s.nrb, dr, sync,
+                                                            mask=1, mref=y)
                 grads["br"] = K.bn_bwd_reduce(dr, M2, Cout)[:, 0].clone()
             # residual conv (1x1, stride s, bias): data grad (transposed), weight grad
             wrTp, cq, kq = packs.wrT if packs is not None else \
-                K.pack_weight(wr.detach().float().view(Cout, Cin).t().unsqueeze(0), dtype)
+                K.pack_weight(_f32(s.wr).view(Cout, Cin).t().unsqueeze(0), dtype)
             grads["wr"] = K.conv_wgrad_w(x, dr, Cin, Cout, T, T_out, Kt=1, stride=stride, pad=0).view(Cout, Cin, 1, 1)
             K.conv_rows(dr, wrTp, Cout, Cin, cq, kq, T_out, T, Kt=1, stride=stride, pad=0, trans=True, out=dx)
             dx_written = True
@@ -434,61 +473,46 @@ class StgcnLayerFunction(torch.autograd.Function):
         wtTp, cq, kq = packs.wtT if packs is not None else \
             K.pack_weight(wt.detach().float().squeeze(-1).permute(2, 1, 0), dtype, stride=stride, trans=True)
         if norm == BN:
-            pro1, hin = dict(pro=1, pro_a=sc1, pro_b=sh1), g
-        else:  # the forward's h = relu(LN1(g)), recomputed when the forward did not keep it (fused route)
+            pro1, hin = dict(pro=1, pro_a=s.sc1, pro_b=s.sh1), g
+        else:  # the forward's h = relu(LN1(g)), recomputed should a forward route not keep it
             pro1 = {}
-            hin = h if h is not None else K.ln_apply(g, ls1, _flat_ln(n1w), _flat_ln(n1b), M1, V, Cout, relu=True)
+            hin = s.h if s.h is not None else \
+                K.ln_apply(g, st1, _flat_ln(s.n1w), _flat_ln(s.n1b), M1, V, Cout, relu=True)
         grads["wt"] = K.conv_wgrad_w(hin, du, Cout, Cout, T, T_out, Kt=kt, stride=stride, pad=pad,
                                      **pro1).unsqueeze(-1)  # (co, ci, Kt, 1)
         if K.tconv_frame_ok(Cout, kt, stride, V, dtype) and getattr(wtTp, "frag_stride", None) == 1:
             dh = K.tconv_frame(du, wtTp, cq, kq, trans=True)
         else:
             dh = K.conv_rows(du, wtTp, Cout, Cout, cq, kq, T_out, T, Kt=kt, stride=stride, pad=pad, trans=True)
-        if not bt_done:
+        if not fused:
             grads["bt"] = K.bn_bwd_reduce(du, M2, Cout)[:, 0].clone()
 
         # ---- through relu(norm1(g))
         dg = K.cl_empty(N, Cout, T, V, dtype, dev)
         if fused:
-            s1, _ = K.bn_bwd_fused(dh, M1, Cout, mask=2, mref=g, msc=sc1, msh=sh1, x1=g, mr1=mr1,
-                                   g1=n1w.detach().float(), out1=dg, sync=sync)
+            s1, _ = K.bn_bwd_fused(dh, M1, Cout, mask=2, mref=g, msc=s.sc1, msh=s.sh1, x1=g, mr1=st1,
+                                   g1=_f32(s.n1w), out1=dg, sync=sync)
             grads["n1w"], grads["n1b"] = s1[1], s1[0]
-        elif norm == BN:
-            s1 = K.bn_bwd_reduce(dh, M1, Cout, mask=2, mref=g, msc=sc1, msh=sh1, x=g, mean_rstd=mr1)
-            grads["n1w"], grads["n1b"] = s1[:, 1].clone(), s1[:, 0].clone()
-            if sync is not None:
-                sync.all_reduce_sums(s1, M1)
-            K.bn_bwd_apply(dh, M1, Cout, dg, mask=2, mref=g, msc=sc1, msh=sh1, x=g, mean_rstd=mr1,
-                           gamma=n1w.detach().float(), sums=s1)
-        else:
-            dgb1 = torch.zeros((2, Cout * V), dtype=torch.float32, device=dev)
-            K.ln_bwd(dh, g, ls1, _flat_ln(n1w), _flat_ln(n1b), N * T, V, Cout, dg, mask=2, dgb=dgb1)
-            grads["n1w"], grads["n1b"] = dgb1[0].view(n1w.shape), dgb1[1].view(n1b.shape)
+        else:  # the mask is relu(norm1(g)) > 0: the BatchNorm kernels recompute it from g, scale1, shift1
+            m1 = dict(mask=2, mref=g, msc=s.sc1, msh=s.sh1) if norm == BN else dict(mask=2)
+            grads["n1w"], grads["n1b"] = _norm_backward(norm, dh, g, st1, s.n1w, s.n1b, dg, sync, **m1)
 
         # ---- graph convolution backward
-        bgp = bg.detach().float().view(P, Cout)
         if ctx.sup is not None:
             # data grad: same gather GEMM on dg over the reverse lists with transposed effective weights;
             # weight / adjacency / bias grads through the per-joint dWeff[w][j] = sum_i dg[(i,w)] x[(i,S(w)_j)]^T blocks
             sup = ctx.sup
-            wg2 = wg.detach().float().reshape(P * Cout, Cin).contiguous()
-            _gconv_wgrad_dweff(ctx, x, dg, A32, wg, wg2, bg, bgp, sup, grads, zero_targets, P, Cin, Cout, T, V, M1,
-                               dtype, dev)
-            dA = grads.pop("dA")
+            wg2 = _f32(wg).reshape(P * Cout, Cin)
+            dA, grads["wg"], grads["bg"] = _gconv_wgrad_dweff(x, dg, A32, wg2, bg, sup,
+                                                              cfg.dense_dA and ctx.needs_input_grad[1], zero_targets,
+                                                              dtype)
             wgT = packs.gwT if packs is not None and packs.gwT is not None else \
                 K.gconv_weights(A32, wg2, sup, Cout, Cin, True, dtype)
             K.gconv(dg, wgT, sup, Cout, Cin, trans=True, out=dx, accumulate=dx_written,
                     res=(dy, ybits) if res_in_gconv else None)
         else:
-            # DW[(n,t,w)][p*Cin+ci] = sum_c dg[(n,t,w)][c] Wg[p*Cout+c][ci]
-            wgT = wg.detach().float().view(P, Cout, Cin).permute(0, 2, 1).reshape(1, P * Cin, Cout)
-            wgTp, cq, kq = K.pack_weight(wgT, dtype)
-            DW = K.conv_rows(dg, wgTp, Cout, P * Cin, cq, kq, T, T)
-            K.amix_trans(DW, A32, Cin, dx, accumulate=dx_written)
-            dA = K.amix_dA(x, DW, A32)
-            dwg = K.conv_wgrad(XA, dg, P * Cin, Cout, T, T, Kt=1)              # [1][Cout][P*Cin]
-            grads["wg"] = dwg.view(Cout, P, Cin).permute(1, 0, 2).reshape(P * Cout, Cin, 1, 1)
-            dA = _bias_through_A(dA, A32, bg, bgp, dg, None, zero_targets()[2], M1, Cout, V, grads)
+            dA, grads["wg"], grads["bg"] = gcn_backward(x, A32, s.XA, wg, bg, dg, dx, dx_written, dtype,
+                                                        z_S=zero_targets()[2])
 
         def gr(name, like):
             v = grads.get(name)
@@ -496,58 +520,53 @@ class StgcnLayerFunction(torch.autograd.Function):
                 return None
             return v.to(like.dtype).view(like.shape)
 
-        wr_, br_, nrw_, nrb_ = (wr, None, nrw, nrb) if res_conv else (None, None, None, None)
-        return (dx, dA.to(ctx.in_dtype), gr("wg", wg), gr("bg", bg), gr("n1w", n1w), gr("n1b", n1b), gr("wt", wt),
-                grads["bt"], gr("n2w", n2w), gr("n2b", n2b), gr("wr", wr_),
+        wr_, nrw_, nrb_ = (s.wr, s.nrw, s.nrb) if res_conv else (None, None, None)
+        return (dx, dA.to(ctx.in_dtype), gr("wg", wg), gr("bg", bg), gr("n1w", s.n1w), gr("n1b", s.n1b), gr("wt", wt),
+                grads["bt"], gr("n2w", s.n2w), gr("n2b", s.n2b), gr("wr", wr_),
                 grads.get("br"), gr("nrw", nrw_), gr("nrb", nrb_), None)
 
 
-def _bias_through_A(dA, A32, bg, bgp, dg, S_fused, z_S, M1, Cout, V, grads):
-    """Bias pushed through A: dA[p][v][w] += sum_c b_p[c] S[w][c] (independent of v), S = per-joint row
-    sums of dg (already produced by the joint-grouped weight-gradient kernel when S_fused is given);
-    sets grads["bg"] and returns dA."""
-    if A32.dim() == 4:
-        Sn = K.rowgroup_sum(dg, M1, Cout, V, per_sample=True, out=z_S)   # [N][V(w)][Cout]
-        dA = dA + torch.einsum("pc,nwc->npw", bgp, Sn).unsqueeze(2)
-        colsum = A32.sum(dim=2)                                         # [N][P][W]
-        grads["bg"] = torch.einsum("npw,nwc->pc", colsum, Sn).reshape(-1)
-        return dA
-    S = S_fused if S_fused is not None else K.rowgroup_sum(dg, M1, Cout, V, out=z_S)   # [V(w)][Cout]
-    if not dA.is_contiguous():
-        dA = dA.contiguous()
-    grads["bg"] = K.gcn_bias_bwd(A32, bg.detach().float().contiguous(), S, dA, Cout)
-    return dA
+def _norm_backward(norm, dy, x, st, gamma, beta, out, sync=None, **mask):
+    """Backward of one norm (norm1, norm2, a residual norm) of rows x (N, C, T, V) with saved (mean, rstd) ``st``:
+    the input gradient of ``dy`` (under ``mask``: the kernels' mask / mref / msc / msh arguments) into ``out``.
+    BatchNorm: reduce, SyncBatchNorm exchange of the sums, apply; LayerNorm: ln_bwd.  Returns (dgamma, dbeta),
+    this rank's own."""
+    N, C, T, V = x.shape
+    M = N * T * V
+    if norm == BN:
+        sums = K.bn_bwd_reduce(dy, M, C, x=x, mean_rstd=st, **mask)
+        dgamma, dbeta = sums[:, 1].clone(), sums[:, 0].clone()
+        if sync is not None:
+            sync.all_reduce_sums(sums, M)
+        K.bn_bwd_apply(dy, M, C, out, x=x, mean_rstd=st, gamma=_f32(gamma), sums=sums, **mask)
+        return dgamma, dbeta
+    dgb = torch.zeros((2, C * V), dtype=torch.float32, device=x.device)
+    K.ln_bwd(dy, x, st, _flat_ln(gamma), _flat_ln(beta), N * T, V, C, out, dgb=dgb, **mask)
+    return dgb[0].view(gamma.shape), dgb[1].view(beta.shape)
 
 
-def _gconv_wgrad_dweff(ctx, x, dg, A32, wg, wg2, bg, bgp, sup, grads, zero_targets, P, Cin, Cout, T, V, M1, dtype,
-                       dev):
-    """Graph-conv weight / adjacency / bias gradients through the per-joint dWeff[w][j] = sum_i dg[(i,w)]
-    x[(i,S(w)_j)]^T blocks (gconv_wgrad + finish).
-    Sets grads["wg"], grads["bg"], grads["dA"]."""
+def _gconv_wgrad_dweff(x, dg, A32, wg2, bg, sup, dense_dA, zero_targets, dtype):
+    """Graph-conv weight / adjacency / bias gradients of the gathered route through the per-joint
+    dWeff[w][j] = sum_i dg[(i,w)] x[(i,S(w)_j)]^T blocks (gconv_wgrad + finish).  ``dense_dA``: caller-owned A,
+    whose gradient is also wanted off the support.  Returns (dA, dWg [P*Cout][Cin], dbg)."""
+    N, Cin, T, V = x.shape
+    P, Cout = A32.shape[-3], dg.shape[1]
     fuse_s = A32.dim() == 3 and K.gconv_wgrad_rowsum_ok(sup, Cin, Cout, dtype)
-    dense_dA = ctx.cfg[6] and ctx.needs_input_grad[1]
     # row sums: overwritten by the joint-grouped wgrad kernel
-    S_rows = torch.empty((V, Cout), dtype=torch.float32, device=dev) if fuse_s else None
+    S_rows = torch.empty((V, Cout), dtype=torch.float32, device=x.device) if fuse_s else None
     dweff = K.gconv_wgrad(x, dg, sup, Cin, Cout, rowsum=S_rows)
     if fuse_s and not dense_dA and K.gconv_finish_bias_ok(A32, sup):
         # dW, dA (support + bias through A) and db in two launches, outputs overwritten
-        dwg2, dA, grads["bg"] = K.gconv_finish_bias(dweff, A32, wg2, sup, Cout, Cin, bg.detach().float().contiguous(),
-                                                    S_rows)
-        dA_done = True
-    else:
-        z_dwg, z_dA, z_S = zero_targets()
-        dwg2, dA = K.gconv_finish(dweff, A32, wg2, sup, Cout, Cin, dW=z_dwg, dA=z_dA)
-        dA_done = False
-    grads["wg"] = dwg2.view(P * Cout, Cin, 1, 1)
+        dwg2, dA, dbg = K.gconv_finish_bias(dweff, A32, wg2, sup, Cout, Cin, _f32(bg), S_rows)
+        return dA, dwg2, dbg
+    z_dwg, z_dA, z_S = zero_targets()
+    dwg2, dA = K.gconv_finish(dweff, A32, wg2, sup, Cout, Cin, dW=z_dwg, dA=z_dA)
     if dense_dA:
-        # caller-owned A: the reference's dA is dense (also off the graph's support), so take
-        # it from the A-first factorisation dA_p[v][w] = sum x[(i,v)] . (dg W_p)[(i,w)]
-        wgTd = wg.detach().float().view(P, Cout, Cin).permute(0, 2, 1).reshape(1, P * Cin, Cout)
-        wgTp, cq, kq = K.pack_weight(wgTd, dtype)
-        dA = K.amix_dA(x, K.conv_rows(dg, wgTp, Cout, P * Cin, cq, kq, T, T), A32)
-    if not dA_done:
-        dA = _bias_through_A(dA, A32, bg, bgp, dg, S_rows, zero_targets()[2], M1, Cout, V, grads)
-    grads["dA"] = dA
+        # the reference's dA is dense (also off the graph's support), so take it from the A-first
+        # factorisation dA_p[v][w] = sum x[(i,v)] . (dg W_p)[(i,w)]
+        dA = K.amix_dA(x, _gcn_dgrad_rows(dg, wg2, P, Cin, Cout, T, dtype), A32)
+    dA, dbg = _bias_through_A(dA, A32, bg, dg, S=S_rows, z_S=z_S)
+    return dA, dwg2, dbg
 
 
 @K.on_tensor_device
@@ -557,15 +576,8 @@ class GcnFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, A, wg, bg, dtype):
         x = K.to_rows(x, dtype)
-        N, Cin, T, V = x.shape
-        P = A.shape[-3]
-        Cout = wg.shape[0] // P
-        A32 = A.detach().float().contiguous()
-        XA = K.amix_fwd(x, A32)
-        wg3 = wg.detach().float().view(P, Cout, Cin).permute(1, 0, 2).reshape(1, Cout, P * Cin)
-        wgp, cp, kp = K.pack_weight(wg3, dtype)
-        bias2d = K.gcn_bias(A32, bg.detach().float().contiguous(), N, Cout)
-        g = K.conv_rows(XA, wgp, P * Cin, Cout, cp, kp, T, T, bias=bias2d, bias_mode=3 if A32.dim() == 4 else 2)
+        A32 = _f32(A)
+        XA, g, _ = gcn_forward(x, A32, wg, bg, dtype)
         ctx.save_for_backward(x, A32, XA, wg, bg)
         ctx.meta = (dtype, A.dtype)
         return g
@@ -574,28 +586,8 @@ class GcnFunction(torch.autograd.Function):
     def backward(ctx, dg):
         x, A32, XA, wg, bg = ctx.saved_tensors
         dtype, adt = ctx.meta
-        N, Cin, T, V = x.shape
-        P = A32.shape[-3]
-        Cout = wg.shape[0] // P
-        dg = K.to_rows(dg, dtype)
-        M = N * T * V
-        wgT = wg.detach().float().view(P, Cout, Cin).permute(0, 2, 1).reshape(1, P * Cin, Cout)
-        wgTp, cq, kq = K.pack_weight(wgT, dtype)
-        DW = K.conv_rows(dg, wgTp, Cout, P * Cin, cq, kq, T, T)
-        dx = K.cl_empty(N, Cin, T, V, dtype, x.device)
-        K.amix_trans(DW, A32, Cin, dx, accumulate=False)
-        dA = K.amix_dA(x, DW, A32)
-        bgp = bg.detach().float().view(P, Cout)
-        if A32.dim() == 4:
-            Sn = K.rowgroup_sum(dg, M, Cout, V, per_sample=True)
-            dA += torch.einsum("pc,nwc->npw", bgp, Sn).unsqueeze(2)
-            dbg = torch.einsum("npw,nwc->pc", A32.sum(dim=2), Sn).reshape(-1)
-        else:
-            S = K.rowgroup_sum(dg, M, Cout, V)
-            dA += (bgp @ S.t()).unsqueeze(1)
-            dbg = (A32.sum(dim=1) @ S).reshape(-1)
-        dwg = K.conv_wgrad(XA, dg, P * Cin, Cout, T, T, Kt=1)
-        dwg = dwg.view(Cout, P, Cin).permute(1, 0, 2).reshape(P * Cout, Cin, 1, 1)
+        dx = K.cl_empty(*x.shape, dtype, x.device)
+        dA, dwg, dbg = gcn_backward(x, A32, XA, wg, bg, K.to_rows(dg, dtype), dx, False, dtype)
         return dx, dA.to(adt), dwg.to(wg.dtype), dbg.to(bg.dtype), None
 
 
@@ -620,7 +612,7 @@ class Conv1x1Function(torch.autograd.Function):
         Cout, Ci = w.shape[0], w.shape[1]
         wp, cp, kp = packs[0] if packs is not None else \
             K.pack_weight(w.detach().float().view(Cout, Ci).unsqueeze(0), dtype)
-        y = K.conv_rows(x, wp, Cin, Cout, cp, kp, T, T, bias=b.detach().float().contiguous())
+        y = K.conv_rows(x, wp, Cin, Cout, cp, kp, T, T, bias=_f32(b))
         ctx.save_for_backward(x, w)
         ctx.dtype = dtype
         ctx.packT = packs[1] if packs is not None else None
@@ -897,8 +889,7 @@ class RtOfflineLayerFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, A, wc, bc, nw, nb, wr, nrw, nrb, cfg):
-        Kt, S, residual, norm, dtype = cfg[:5]
-        sync = cfg[5] if len(cfg) > 5 else None
+        Kt, S, residual, norm, dtype, sync = cfg.Kt, cfg.S, cfg.residual, cfg.norm, cfg.dtype, cfg.sync
         bn_finalize = sync.finalize if sync is not None else K.bn_finalize
         dev = x.device
         x = K.to_rows(x, dtype)
@@ -906,31 +897,28 @@ class RtOfflineLayerFunction(torch.autograd.Function):
         P = A.shape[-3]
         Cout = wc.shape[0] // P
         M = N * L * V
-        A32 = A.detach().float().contiguous()
+        A32 = _f32(A)
         res_conv = residual and not (Cin == Cout and S == 1)
         XA, z, _ = gcn_forward(x, A32, wc, bc, dtype)
         b = K.box_sum(z, Kt, S)
         relu_mode = 3 if residual else 2
-        r = None
+        r = str_ = None
         if res_conv:
-            wrp, cq, kq = K.pack_weight(wr.detach().float().view(1, Cout, Cin), dtype)
+            wrp, cq, kq = K.pack_weight(_f32(wr).view(1, Cout, Cin), dtype)
             if norm == BN:
                 str_, _ = gcn_stats_buffer(M, Cout, dev)
-            r = K.conv_rows(x, wrp, Cin, Cout, cq, kq, L, L, stats=str_ if norm == BN else None)
+            r = K.conv_rows(x, wrp, Cin, Cout, cq, kq, L, L, stats=str_)
         if norm == BN:
             part, nbk, _ = K.bn_stats_partial(b, M, Cout)
-            mr, sc, sh = bn_finalize(part, nbk, Cout, Cout, nw.detach().float(), nb.detach().float())
+            st, sc, sh = bn_finalize(part, nbk, Cout, Cout, _f32(nw), _f32(nb))
             if res_conv:
-                mrr, scr, shr = bn_finalize(str_, str_.shape[0], str_.shape[1], Cout, nrw.detach().float(),
-                                              nrb.detach().float())
+                stn, scr, shr = bn_finalize(str_, str_.shape[0], str_.shape[1], Cout, _f32(nrw), _f32(nrb))
                 y = K.bn_apply(b, sc, sh, M, Cout, res_mode=2, r=r, rsc=scr, rsh=shr, relu=relu_mode)
             else:
                 y = K.bn_apply(b, sc, sh, M, Cout, res_mode=1 if residual else 0, r=x if residual else None,
                                relu=relu_mode)
-            st, stn = mr, (mrr if res_conv else None)
         else:
             st = K.ln_stats(b, N * L, V, Cout)
-            stn = None
             if res_conv:
                 stn = K.ln_stats(r, N * L, V, Cout)
                 y = K.ln_apply(b, st, _flat_ln(nw), _flat_ln(nb), M, V, Cout, res_mode=2, r=r, rst=stn,
@@ -938,30 +926,25 @@ class RtOfflineLayerFunction(torch.autograd.Function):
             else:
                 y = K.ln_apply(b, st, _flat_ln(nw), _flat_ln(nb), M, V, Cout, res_mode=1 if residual else 0,
                                r=x if residual else None, relu=relu_mode)
-        ctx.cfg = cfg
-        ctx.dims = (N, Cin, Cout, L, V, P, res_conv)
-        ctx.in_dtype = A.dtype
-        saved = [x, A32, XA, b, y, st, wc, bc, nw, nb]
+        # st / stn: (mean, rstd) of the norm / the residual norm
+        saved = dict(x=x, A32=A32, XA=XA, b=b, y=y, st=st, wc=wc, bc=bc, nw=nw, nb=nb)
         if norm == BN:
-            saved += [sc, sh]
+            saved.update(sc=sc, sh=sh)
         if res_conv:
-            saved += [r, stn, wr, nrw, nrb]
-        ctx.save_for_backward(*saved)
+            saved.update(r=r, stn=stn, wr=wr, nrw=nrw, nrb=nrb)
+        _save_named(ctx, **saved)
+        ctx.cfg = cfg
+        ctx.res_conv = res_conv
+        ctx.in_dtype = A.dtype
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        Kt, S, residual, norm, dtype = ctx.cfg[:5]
-        sync = ctx.cfg[5] if len(ctx.cfg) > 5 else None
-        N, Cin, Cout, L, V, P, res_conv = ctx.dims
-        sv = list(ctx.saved_tensors)
-        x, A32, XA, b, y, st, wc, bc, nw, nb = sv[:10]
-        rest = sv[10:]
-        if norm == BN:
-            sc, sh = rest[:2]
-            rest = rest[2:]
-        if res_conv:
-            r, stn, wr, nrw, nrb = rest
+        cfg, s, res_conv = ctx.cfg, _saved(ctx), ctx.res_conv
+        Kt, S, residual, norm, dtype, sync = cfg.Kt, cfg.S, cfg.residual, cfg.norm, cfg.dtype, cfg.sync
+        x, b, y = s.x, s.b, s.y
+        N, Cin, L, V = x.shape
+        Cout = b.shape[1]
         dev = x.device
         M = N * L * V
         dy = K.to_rows(dy, dtype)
@@ -976,43 +959,25 @@ class RtOfflineLayerFunction(torch.autograd.Function):
         g = {}
         if res_conv:
             dr = K.cl_empty(N, Cout, L, V, dtype, dev)
-            if norm == BN:
-                sr = K.bn_bwd_reduce(dq, M, Cout, x=r, mean_rstd=stn)
-                g["nrw"], g["nrb"] = sr[:, 1].clone(), sr[:, 0].clone()
-                if sync is not None:
-                    sync.all_reduce_sums(sr, M)
-                K.bn_bwd_apply(dq, M, Cout, dr, x=r, mean_rstd=stn, gamma=nrw.detach().float(), sums=sr)
-            else:
-                dgbr = torch.zeros((2, Cout * V), dtype=torch.float32, device=dev)
-                K.ln_bwd(dq, r, stn, _flat_ln(nrw), _flat_ln(nrb), N * L, V, Cout, dr, dgb=dgbr)
-                g["nrw"], g["nrb"] = dgbr[0].view(nrw.shape), dgbr[1].view(nrb.shape)
-            wrT, cq, kq = K.pack_weight(wr.detach().float().view(Cout, Cin).t().reshape(1, Cin, Cout), dtype)
+            g["nrw"], g["nrb"] = _norm_backward(norm, dq, s.r, s.stn, s.nrw, s.nrb, dr, sync)
+            wrT, cq, kq = K.pack_weight(_f32(s.wr).view(Cout, Cin).t().reshape(1, Cin, Cout), dtype)
             K.conv_rows(dr, wrT, Cout, Cin, cq, kq, L, L, trans=True, out=dx)
             dx_written = True
             g["wr"] = K.conv_wgrad_w(x, dr, Cin, Cout, L, L).view(Cout, Cin, 1, 1)
         elif residual:
             K.bn_bwd_apply(dq, M, Cin, dx)  # dx = dq
             dx_written = True
-        # through relu(norm(b))
+        # through relu(norm(b)): the BatchNorm kernels recompute the mask from b, scale, shift
         db = K.cl_empty(N, Cout, L, V, dtype, dev)
-        if norm == BN:
-            s1 = K.bn_bwd_reduce(dq, M, Cout, mask=2, mref=b, msc=sc, msh=sh, x=b, mean_rstd=st)
-            g["nw"], g["nb"] = s1[:, 1].clone(), s1[:, 0].clone()
-            if sync is not None:
-                sync.all_reduce_sums(s1, M)
-            K.bn_bwd_apply(dq, M, Cout, db, mask=2, mref=b, msc=sc, msh=sh, x=b, mean_rstd=st,
-                           gamma=nw.detach().float(), sums=s1)
-        else:
-            dgb = torch.zeros((2, Cout * V), dtype=torch.float32, device=dev)
-            K.ln_bwd(dq, b, st, _flat_ln(nw), _flat_ln(nb), N * L, V, Cout, db, mask=2, dgb=dgb)
-            g["nw"], g["nb"] = dgb[0].view(nw.shape), dgb[1].view(nb.shape)
+        m = dict(mask=2, mref=b, msc=s.sc, msh=s.sh) if norm == BN else dict(mask=2)
+        g["nw"], g["nb"] = _norm_backward(norm, dq, b, s.st, s.nw, s.nb, db, sync, **m)
         dz = K.box_sum(db, Kt, S, trans=True)
-        dA, dwc, dbc = gcn_backward(x, A32, XA, wc, bc, dz, dx, dx_written, dtype)
+        dA, dwc, dbc = gcn_backward(x, s.A32, s.XA, s.wc, s.bc, dz, dx, dx_written, dtype)
 
         def gr(name, like):
             v = g.get(name)
             return None if v is None or like is None or not like.requires_grad else v.to(like.dtype).view(like.shape)
 
-        return (dx, dA.to(ctx.in_dtype), dwc.to(wc.dtype), dbc.to(bc.dtype), gr("nw", nw), gr("nb", nb),
-                gr("wr", wr if res_conv else None), gr("nrw", nrw if res_conv else None),
-                gr("nrb", nrb if res_conv else None), None)
+        return (dx, dA.to(ctx.in_dtype), dwc.to(s.wc.dtype), dbc.to(s.bc.dtype), gr("nw", s.nw), gr("nb", s.nb),
+                gr("wr", s.wr if res_conv else None), gr("nrw", s.nrw if res_conv else None),
+                gr("nrb", s.nrb if res_conv else None), None)

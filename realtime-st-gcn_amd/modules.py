@@ -166,9 +166,10 @@ class StgcnLayer(nn.Module):
         # keeps nothing for a backward
         infer = not torch.is_grad_enabled() or not (
             x.requires_grad or A.requires_grad or any(p.requires_grad for p in self.parameters()))
-        cfg = (self.kernel_size[0], self.stride, self.is_residual, self.normalization, self.compute_dtype,
-               self.graph_support(A), not self._graph_bound, infer, self._fused_cache, None if infer else packs,
-               active_sync(self))
+        cfg = F_.LayerCfg(kt=self.kernel_size[0], stride=self.stride, residual=self.is_residual,
+                          norm=self.normalization, dtype=self.compute_dtype, sup=self.graph_support(A),
+                          dense_dA=not self._graph_bound, infer=infer, cache=self._fused_cache,
+                          packs=None if infer else packs, sync=active_sync(self))
         return F_.StgcnLayerFunction.apply(x, A, self.gcn.conv.weight, self.gcn.conv.bias, n1.weight, n1.bias,
                                            conv.weight, conv.bias, n2.weight, n2.bias, wr, br, nrw, nrb, cfg)
 

@@ -7,13 +7,12 @@ HIP stream; all arithmetic happens in the HIP kernels.
 """
 from __future__ import annotations
 
-
 import ctypes
 
 import torch
 
 from . import _lib as L
-from .routing import ROUTING
+
 
 class device_of:
     """Device guard (SURVEY 8(b) threading): make the device of tensor ``t`` current for the body, so that
@@ -72,13 +71,26 @@ EVENT_HOOK = None
 KTIME_HOOK = None
 
 
-def _k_start(h, family, shape, flop=None, nbytes=None):
-    """Report a kernel-wrapper launch to the hook ``h`` (= KTIME_HOOK, checked by the caller so that the
-    uninstrumented path costs one global read): tag ``"k:<family>:<shape>"``, work ``{"flop": algorithmic
-    flops, "bytes": algorithmic HBM bytes}`` — bench.py's per-kernel table.  Returns the tag for _k_end."""
-    tag = f"k:{family}:{shape}"
-    h(tag, "start", {"flop": flop, "bytes": nbytes})
-    return tag
+def _launch(name, fn, *args, kinfo=None, tag=None):
+    """``L.check(fn(*args), name)`` inside the start / end bracket of both hooks.  ``kinfo``: callable ->
+    (family, shape, algorithmic flops or None, algorithmic HBM bytes) of an instrumented wrapper, evaluated only
+    with a hook installed (each hook costs one global read otherwise); KTIME_HOOK gets tag "k:<family>:<shape>"
+    and work {"flop", "bytes"}.  ``tag``: the caller's EVENT_HOOK tag, the outer bracket, its work the flops."""
+    hook = EVENT_HOOK if tag is not None else None
+    h = KTIME_HOOK if kinfo is not None else None
+    if not hook and not h:
+        return L.check(fn(*args), name)
+    family, shape, flop, nbytes = kinfo() if kinfo is not None else (None, None, None, None)
+    if hook:
+        hook(tag, "start", flop)
+    if h:
+        ktag = f"k:{family}:{shape}"
+        h(ktag, "start", {"flop": flop, "bytes": nbytes})
+    L.check(fn(*args), name)
+    if h:
+        h(ktag, "end", None)
+    if hook:
+        hook(tag, "end", None)
 
 
 def _dense(A: torch.Tensor) -> torch.Tensor:
@@ -235,6 +247,20 @@ class PrepPlan:
                                        L.stream()), "prep_run")
 
 
+def _conv_desc(x, out, w3p, w_frag, T_in, T_out, Cin, Cout, cp, kp, Kt, stride, pad, trans, bias, pro, pro_a, pro_b,
+               stats):
+    """The ConvDesc of conv_rows / tconv_frame: rows x -> out, bias_mode 1 with a bias, not accumulating."""
+    d = L.ConvDesc()
+    d.in_, d.out, d.w, d.w_frag = x.data_ptr(), out.data_ptr(), w3p.data_ptr(), w_frag
+    d.bias, d.pro_a, d.pro_b, d.stats = L.ptr(bias), L.ptr(pro_a), L.ptr(pro_b), L.ptr(stats)
+    d.N, d.T_in, d.T_out, d.V, d.Cin, d.Cout, d.Cin_pad, d.Cout_pad = \
+        x.shape[0], T_in, T_out, x.shape[3], Cin, Cout, kp, cp
+    d.Kt, d.stride, d.pad, d.trans, d.pro = Kt, stride, pad, int(trans), pro
+    d.bias_mode, d.accumulate = 0 if bias is None else 1, 0
+    d.in_ld, d.out_ld = rows_ld(x), rows_ld(out)
+    return d
+
+
 def conv_rows(x, w3p, Cin, Cout, cp, kp, T_in, T_out, Kt=1, stride=1, pad=0, trans=False, bias=None, bias_mode=None,
               pro=0, pro_a=None, pro_b=None, pro_stats=None, stats=None, out=None, accumulate=False, tag=None):
     """Implicit-GEMM row conv (stgcn_conv_rows).  x rows: [N, T_in, V, Cin] (any channels-last view).
@@ -244,31 +270,16 @@ def conv_rows(x, w3p, Cin, Cout, cp, kp, T_in, T_out, Kt=1, stride=1, pad=0, tra
     N, V = x.shape[0], x.shape[3]
     if out is None:
         out = cl_empty(N, Cout, T_out, V, x.dtype, x.device)
-    d = L.ConvDesc()
-    d.in_, d.out, d.w = x.data_ptr(), out.data_ptr(), w3p.data_ptr()
     fs = getattr(w3p, "frag_stride", None)
-    d.w_frag = getattr(w3p, "frag_ptr", None) if fs is not None and fs in (stride, 0) else None
-    d.bias = L.ptr(bias)
-    d.pro_a, d.pro_b, d.pro_stats = L.ptr(pro_a), L.ptr(pro_b), L.ptr(pro_stats)
-    d.stats = L.ptr(stats)
-    d.N, d.T_in, d.T_out, d.V, d.Cin, d.Cout, d.Cin_pad, d.Cout_pad = N, T_in, T_out, V, Cin, Cout, kp, cp
-    d.Kt, d.stride, d.pad, d.trans, d.pro = Kt, stride, pad, int(trans), pro
-    d.bias_mode = (0 if bias is None else 1) if bias_mode is None else bias_mode
+    d = _conv_desc(x, out, w3p, getattr(w3p, "frag_ptr", None) if fs is not None and fs in (stride, 0) else None,
+                   T_in, T_out, Cin, Cout, cp, kp, Kt, stride, pad, trans, bias, pro, pro_a, pro_b, stats)
+    d.pro_stats = L.ptr(pro_stats)
+    if bias_mode is not None:
+        d.bias_mode = bias_mode
     d.accumulate = int(accumulate)
-    d.in_ld, d.out_ld = rows_ld(x), rows_ld(out)
-    hook = EVENT_HOOK if tag is not None else None
-    if hook:  # (tag, phase, algorithmic flops of the launch)
-        hook(tag, "start", 2.0 * N * T_out * V * Cout * Cin * Kt)
-    h = KTIME_HOOK
-    if h:
-        fam = ("tcn_dgrad" if trans else "tcn_fwd") if Kt > 1 else "conv1x1"
-        ktag = _k_start(h, fam, f"{Cin}->{Cout} s{stride}", 2.0 * N * T_out * V * Cout * Cin * Kt,
-                        x.element_size() * N * V * (T_in * Cin + T_out * Cout))
-    L.check(L.lib().stgcn_conv_rows(d, L.dtype_code(x.dtype), L.stream()), "conv_rows")
-    if h:
-        h(ktag, "end", None)
-    if hook:
-        hook(tag, "end", None)
+    _launch("conv_rows", L.lib().stgcn_conv_rows, d, L.dtype_code(x.dtype), L.stream(), tag=tag, kinfo=lambda: (
+        ("tcn_dgrad" if trans else "tcn_fwd") if Kt > 1 else "conv1x1", f"{Cin}->{Cout} s{stride}",
+        2.0 * N * T_out * V * Cout * Cin * Kt, x.element_size() * N * V * (T_in * Cin + T_out * Cout)))
     return out
 
 
@@ -291,46 +302,40 @@ def tconv_frame(x, w3p, cp, kp, trans=False, bias=None, pro_a=None, pro_b=None, 
     if getattr(w3p, "frag_stride", None) != 1:
         raise RuntimeError("stgcn_amd: tconv_frame needs the stride-1 fragment image of the weight")
     out = cl_empty(N, C, T, V, x.dtype, x.device)
-    d = L.ConvDesc()
-    d.in_, d.out, d.w, d.w_frag = x.data_ptr(), out.data_ptr(), w3p.data_ptr(), w3p.frag_ptr
-    d.bias, d.pro_a, d.pro_b, d.stats = L.ptr(bias), L.ptr(pro_a), L.ptr(pro_b), L.ptr(stats)
-    d.N, d.T_in, d.T_out, d.V, d.Cin, d.Cout, d.Cin_pad, d.Cout_pad = N, T, T, V, C, C, kp, cp
-    d.Kt, d.stride, d.pad, d.trans, d.pro = 9, 1, 4, int(trans), 1 if pro_a is not None else 0
-    d.bias_mode, d.accumulate = 0 if bias is None else 1, 0
-    d.in_ld, d.out_ld = rows_ld(x), rows_ld(out)
-    hook = EVENT_HOOK if tag is not None else None
-    flop = 2.0 * N * T * V * C * C * 9
-    if hook:
-        hook(tag, "start", flop)
-    h = KTIME_HOOK
-    if h:
-        ktag = _k_start(h, "tconv_frame_dgrad" if trans else "tconv_frame_fwd", f"{C}->{C} s1", flop,
-                        x.element_size() * N * V * T * 2 * C)
-    L.check(L.lib().stgcn_tconv_frame(d, L.stream()), "tconv_frame")
-    if h:
-        h(ktag, "end", None)
-    if hook:
-        hook(tag, "end", None)
+    d = _conv_desc(x, out, w3p, w3p.frag_ptr, T, T, C, C, cp, kp, 9, 1, 4, trans, bias,
+                   1 if pro_a is not None else 0, pro_a, pro_b, stats)
+    _launch("tconv_frame", L.lib().stgcn_tconv_frame, d, L.stream(), tag=tag, kinfo=lambda: (
+        "tconv_frame_dgrad" if trans else "tconv_frame_fwd", f"{C}->{C} s1", 2.0 * N * T * V * C * C * 9,
+        x.element_size() * N * V * T * 2 * C))
     return out
+
+
+def _wgrad_desc(x, dy, Cin, Cout, T_in, T_out, Kt, stride, pad, pro, pro_a, pro_b, pro_stats):
+    """(WgradDesc without its output, dtype code, workspace or None) of conv_wgrad / conv_wgrad_w.  The workspace
+    (the per-block fp32 partials of the deterministic frame-tiled paths, where the library asks for one) is
+    already in the descriptor; the caller keeps the tensor alive over its launch."""
+    d = L.WgradDesc()
+    d.in_, d.dy = x.data_ptr(), dy.data_ptr()
+    d.pro_a, d.pro_b, d.pro_stats = L.ptr(pro_a), L.ptr(pro_b), L.ptr(pro_stats)
+    d.N, d.T_in, d.T_out, d.V, d.Cin, d.Cout, d.Kt, d.stride, d.pad, d.pro = \
+        x.shape[0], T_in, T_out, x.shape[3], Cin, Cout, Kt, stride, pad, pro
+    d.in_ld, d.dy_ld = rows_ld(x), rows_ld(dy)
+    code = L.dtype_code(x.dtype)
+    nbytes = L.lib().stgcn_conv_wgrad_workspace(d, code)
+    work = None
+    if nbytes > 0:
+        work = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
+        d.work, d.work_bytes = work.data_ptr(), nbytes
+    return d, code, work
 
 
 def conv_wgrad(x, dy, Cin, Cout, T_in, T_out, Kt=1, stride=1, pad=0, pro=0, pro_a=None, pro_b=None, pro_stats=None,
                dw=None):
     """dw[Kt][Cout][Cin] (fp32) += weight gradient (stgcn_conv_wgrad)."""
-    N, V = x.shape[0], x.shape[3]
     if dw is None:
         dw = torch.zeros((Kt, Cout, Cin), dtype=torch.float32, device=x.device)
-    d = L.WgradDesc()
-    d.in_, d.dy, d.dw = x.data_ptr(), dy.data_ptr(), dw.data_ptr()
-    d.pro_a, d.pro_b, d.pro_stats = L.ptr(pro_a), L.ptr(pro_b), L.ptr(pro_stats)
-    d.N, d.T_in, d.T_out, d.V, d.Cin, d.Cout, d.Kt, d.stride, d.pad, d.pro = \
-        N, T_in, T_out, V, Cin, Cout, Kt, stride, pad, pro
-    d.in_ld, d.dy_ld = rows_ld(x), rows_ld(dy)
-    code = L.dtype_code(x.dtype)
-    nbytes = L.lib().stgcn_conv_wgrad_workspace(d, code)
-    if nbytes > 0:  # per-block fp32 partials of the deterministic frame-tiled path
-        work = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
-        d.work, d.work_bytes = work.data_ptr(), nbytes
+    d, code, work = _wgrad_desc(x, dy, Cin, Cout, T_in, T_out, Kt, stride, pad, pro, pro_a, pro_b, pro_stats)
+    d.dw = dw.data_ptr()
     L.check(L.lib().stgcn_conv_wgrad(d, code, L.stream()), "conv_wgrad")
     return dw
 
@@ -338,29 +343,16 @@ def conv_wgrad(x, dy, Cin, Cout, T_in, T_out, Kt=1, stride=1, pad=0, pro=0, pro_
 def conv_wgrad_w(x, dy, Cin, Cout, T_in, T_out, Kt=1, stride=1, pad=0, pro=0, pro_a=None, pro_b=None, pro_stats=None):
     """The weight gradient as a FRESH fp32 tensor in nn.Conv2d weight order (Cout, Cin, Kt): the workspace paths
     write it directly (out_mode 1: no zero fill, no permute copy); the others accumulate into zeros and permute."""
-    N, V = x.shape[0], x.shape[3]
-    d = L.WgradDesc()
-    d.in_, d.dy = x.data_ptr(), dy.data_ptr()
-    d.pro_a, d.pro_b, d.pro_stats = L.ptr(pro_a), L.ptr(pro_b), L.ptr(pro_stats)
-    d.N, d.T_in, d.T_out, d.V, d.Cin, d.Cout, d.Kt, d.stride, d.pad, d.pro = \
-        N, T_in, T_out, V, Cin, Cout, Kt, stride, pad, pro
-    d.in_ld, d.dy_ld = rows_ld(x), rows_ld(dy)
-    code = L.dtype_code(x.dtype)
-    nbytes = L.lib().stgcn_conv_wgrad_workspace(d, code)
-    if nbytes <= 0:
+    d, code, work = _wgrad_desc(x, dy, Cin, Cout, T_in, T_out, Kt, stride, pad, pro, pro_a, pro_b, pro_stats)
+    if work is None:
         return conv_wgrad(x, dy, Cin, Cout, T_in, T_out, Kt, stride, pad, pro, pro_a, pro_b,
                           pro_stats).permute(1, 2, 0).contiguous()
-    work = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
-    d.work, d.work_bytes = work.data_ptr(), nbytes
+    N, V = x.shape[0], x.shape[3]
     dw = torch.empty((Cout, Cin, Kt), dtype=torch.float32, device=x.device)
     d.dw, d.out_mode = dw.data_ptr(), 1
-    h = KTIME_HOOK
-    if h:
-        ktag = _k_start(h, "tcn_wgrad" if Kt > 1 else "wgrad1x1", f"{Cin}->{Cout} s{stride}",
-                        2.0 * N * T_out * V * Cout * Cin * Kt, x.element_size() * N * V * (T_in * Cin + T_out * Cout))
-    L.check(L.lib().stgcn_conv_wgrad(d, code, L.stream()), "conv_wgrad")
-    if h:
-        h(ktag, "end", None)
+    _launch("conv_wgrad", L.lib().stgcn_conv_wgrad, d, code, L.stream(), kinfo=lambda: (
+        "tcn_wgrad" if Kt > 1 else "wgrad1x1", f"{Cin}->{Cout} s{stride}", 2.0 * N * T_out * V * Cout * Cin * Kt,
+        x.element_size() * N * V * (T_in * Cin + T_out * Cout)))
     return dw
 
 
@@ -598,12 +590,7 @@ def layer_fused(x, A, wimg, gbias, wt_packed, tbias, ln, tag=None, residual=Fals
         d.g_ld, d.u_ld = rows_ld(g), rows_ld(u)
         hh = cl_empty(N, C, T, V, x.dtype, x.device)
         d.h_out, d.h_ld = hh.data_ptr(), rows_ld(hh)
-    hook = EVENT_HOOK if tag is not None else None
-    if hook:
-        hook(tag, "start", None)
-    L.check(L.lib().stgcn_layer_fused_fwd(d, L.stream()), "layer_fused")
-    if hook:
-        hook(tag, "end", None)
+    _launch("layer_fused", L.lib().stgcn_layer_fused_fwd, d, L.stream(), tag=tag)
     if train:
         return z, g, u, st[0], st[1], hh
     return z
@@ -628,14 +615,9 @@ def gconv(x, wpk, sup, Cin, Cout, trans=False, bias=None, stats=None, out=None, 
         if accumulate or rbits.dtype != torch.uint8:
             raise RuntimeError("stgcn_amd: gconv's masked residual needs accumulate=False and uint8 sign bits")
         d.res, d.res_bits, d.res_ld = rr.data_ptr(), rbits.data_ptr(), rows_ld(rr)
-    h = KTIME_HOOK
-    if h:
-        ktag = _k_start(h, "gconv_dgrad" if trans else "gconv_fwd", f"{Cin}->{Cout}" if not trans else f"{Cout}->{Cin}",
-                        2.0 * N * T * sup.nnz * Cin * Cout,
-                        x.element_size() * N * T * V * (Cin + Cout * (2 if accumulate else 1)))
-    L.check(L.lib().stgcn_gconv(d, L.dtype_code(x.dtype), L.stream()), "gconv")
-    if h:
-        h(ktag, "end", None)
+    _launch("gconv", L.lib().stgcn_gconv, d, L.dtype_code(x.dtype), L.stream(), kinfo=lambda: (
+        "gconv_dgrad" if trans else "gconv_fwd", f"{Cin}->{Cout}" if not trans else f"{Cout}->{Cin}",
+        2.0 * N * T * sup.nnz * Cin * Cout, x.element_size() * N * T * V * (Cin + Cout * (2 if accumulate else 1))))
     return out
 
 
@@ -659,22 +641,25 @@ def gconv_wgrad(x, dy, sup, Cin, Cout, rowsum=None):
     if nbytes > 0:
         work = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
         d.work, d.work_bytes = work.data_ptr(), nbytes
-    h = KTIME_HOOK
-    if h:
-        ktag = _k_start(h, "gconv_wgrad", f"{Cin}->{Cout}", 2.0 * N * T * sup.nnz * Cin * Cout,
-                        x.element_size() * N * T * V * (Cin + Cout))
-    hook = EVENT_HOOK
-    if hook and gconv_wgrad3_shape(sup, Cin, Cout, x.dtype):
-        # bench.py's roofline: the accumulation kernel (gconv_wgrad3) bracketed alone, then its slab reduction
-        d.phase = 1
-        hook("gconv_wgrad3", "start", {"flop": 2.0 * N * T * sup.nnz * Cin * Cout,
-                                       "bytes": x.element_size() * N * T * V * (Cin + Cout), "shape": f"{Cin}->{Cout}"})
-        L.check(L.lib().stgcn_gconv_wgrad(d, code, L.stream()), "gconv_wgrad")
-        hook("gconv_wgrad3", "end", None)
-        d.phase = 2
-    L.check(L.lib().stgcn_gconv_wgrad(d, code, L.stream()), "gconv_wgrad")
-    if h:
-        h(ktag, "end", None)
+    fn = L.lib().stgcn_gconv_wgrad
+
+    def launches():
+        hook = EVENT_HOOK
+        if hook and gconv_wgrad3_shape(sup, Cin, Cout, x.dtype):
+            # bench.py's roofline: the accumulation kernel (gconv_wgrad3) bracketed alone (its work carries the
+            # shape, so by hand), then its slab reduction
+            d.phase = 1
+            hook("gconv_wgrad3", "start", {"flop": 2.0 * N * T * sup.nnz * Cin * Cout,
+                                           "bytes": x.element_size() * N * T * V * (Cin + Cout),
+                                           "shape": f"{Cin}->{Cout}"})
+            L.check(fn(d, code, L.stream()), "gconv_wgrad")
+            hook("gconv_wgrad3", "end", None)
+            d.phase = 2
+        return fn(d, code, L.stream())
+
+    _launch("gconv_wgrad", launches, kinfo=lambda: (
+        "gconv_wgrad", f"{Cin}->{Cout}", 2.0 * N * T * sup.nnz * Cin * Cout,
+        x.element_size() * N * T * V * (Cin + Cout)))
     return dweff
 
 
@@ -711,15 +696,10 @@ def gconv_finish_bias(dweff, A, W, sup, Cout, Cin, bconv, S):
     dA = out[P * Cout * Cin:P * Cout * Cin + P * V * V].view(P, V, V)
     db = out[P * Cout * Cin + P * V * V:]
     work = _workspace(L.lib().stgcn_gconv_wgrad_finish_workspace(P, V, sup.J, Cout, Cin), dev)
-    h = KTIME_HOOK
-    if h:
-        ktag = _k_start(h, "gconv_wgrad_finish", f"{Cin}->{Cout}", None, 4 * dweff.numel())
-    L.check(L.lib().stgcn_gconv_wgrad_finish_bias(dweff.data_ptr(), A.data_ptr(), W.data_ptr(), sup.nbr.data_ptr(),
-                                                  sup.deg.data_ptr(), P, V, sup.J, Cout, Cin, bconv.data_ptr(),
-                                                  S.data_ptr(), dW.data_ptr(), dA.data_ptr(), db.data_ptr(),
-                                                  work.data_ptr(), L.stream()), "gconv_finish_bias")
-    if h:
-        h(ktag, "end", None)
+    _launch("gconv_finish_bias", L.lib().stgcn_gconv_wgrad_finish_bias, dweff.data_ptr(), A.data_ptr(), W.data_ptr(),
+            sup.nbr.data_ptr(), sup.deg.data_ptr(), P, V, sup.J, Cout, Cin, bconv.data_ptr(), S.data_ptr(),
+            dW.data_ptr(), dA.data_ptr(), db.data_ptr(), work.data_ptr(), L.stream(),
+            kinfo=lambda: ("gconv_wgrad_finish", f"{Cin}->{Cout}", None, 4 * dweff.numel()))
     return dW, dA, db
 
 
@@ -761,20 +741,19 @@ def bn_apply(u, sc, sh, M, C, res_mode=0, r=None, rsc=None, rsh=None, relu=True,
     output's sign bits (stgcn_bn_apply_bits), the backward's ReLU mask at 1/16 of y's bytes (bn_bwd_fused mask 3)."""
     if out is None:
         out = torch.empty_like(u)
-    h = KTIME_HOOK
-    if h:
-        ktag = _k_start(h, "bn_apply", f"C{C}", None, u.element_size() * M * C * (3 if r is not None else 2))
     args = (u.data_ptr(), ldu or rows_ld(u), sc.data_ptr(), sh.data_ptr(), res_mode, L.ptr(r),
             rows_ld(r) if r is not None else 0, L.ptr(rsc), L.ptr(rsh), int(relu), out.data_ptr(),
             ldy or rows_ld(out), M, C)
+
+    def kinfo():
+        return "bn_apply", f"C{C}", None, u.element_size() * M * C * (3 if r is not None else 2)
+
     if bits is not None:
         if u.dtype != torch.bfloat16 or C % 8 or bits.dtype != torch.uint8 or bits.numel() < M * (C // 8):
             raise RuntimeError("stgcn_amd: bn_apply bits need bf16 rows, C % 8 == 0 and a uint8 [M][C/8] buffer")
-        L.check(L.lib().stgcn_bn_apply_bits(*args, bits.data_ptr(), L.stream()), "bn_apply_bits")
+        _launch("bn_apply_bits", L.lib().stgcn_bn_apply_bits, *args, bits.data_ptr(), L.stream(), kinfo=kinfo)
     else:
-        L.check(L.lib().stgcn_bn_apply(*args, L.dtype_code(u.dtype), L.stream()), "bn_apply")
-    if h:
-        h(ktag, "end", None)
+        _launch("bn_apply", L.lib().stgcn_bn_apply, *args, L.dtype_code(u.dtype), L.stream(), kinfo=kinfo)
     return out
 
 
@@ -829,25 +808,18 @@ def bn_bwd_fused(dy, M, C, mask=0, mref=None, msc=None, msh=None, x1=None, mr1=N
     d.ldo1 = rows_ld(out1) if out1 is not None else 0
     d.ldo2 = rows_ld(out2) if out2 is not None else 0
     d.acc2 = int(acc2)
-    h = KTIME_HOOK
-    es = dy.element_size()
-    n_in = sum(t is not None for t in (dy, mref, x1, x2))
-    if h:
-        ktag = _k_start(h, "bn_bwd_reduce", f"C{C}", None, es * M * C * n_in)
-    L.check(L.lib().stgcn_bn_bwd_fused_reduce(d, code, L.stream()), "bn_bwd_fused_reduce")
-    if h:
-        h(ktag, "end", None)
+    def nbytes(n_out):  # algorithmic HBM bytes of a pass: its inputs + n_out outputs
+        return dy.element_size() * M * C * (sum(t is not None for t in (dy, mref, x1, x2)) + n_out)
+
+    _launch("bn_bwd_fused_reduce", L.lib().stgcn_bn_bwd_fused_reduce, d, code, L.stream(),
+            kinfo=lambda: ("bn_bwd_reduce", f"C{C}", None, nbytes(0)))
     if sync is not None and out1 is not None:
         # the reduce pass wrote the per-channel sums twice: float4 rows [C] (what apply reads) and planar [3][C]
         # (returned); only the rows are exchanged
         sync.all_reduce_sums(sums[:4 * C].view(C, 4), M, count_lane=True)
     if out1 is not None:
-        if h:
-            n_out = 1 + (out2 is not None) * (2 if acc2 else 1)
-            ktag = _k_start(h, "bn_bwd_apply", f"C{C}", None, es * M * C * (n_in + n_out))
-        L.check(L.lib().stgcn_bn_bwd_fused_apply(d, code, L.stream()), "bn_bwd_fused_apply")
-        if h:
-            h(ktag, "end", None)
+        _launch("bn_bwd_fused_apply", L.lib().stgcn_bn_bwd_fused_apply, d, code, L.stream(), kinfo=lambda: (
+            "bn_bwd_apply", f"C{C}", None, nbytes(1 + (out2 is not None) * (2 if acc2 else 1))))
     return sums[4 * C:].view(3, C), (osum[4 * C:].view(3, C) if osum is not None else None)
 
 

@@ -61,8 +61,8 @@ class OfflineLayer(nn.Module):
             wr, nrw, nrb = self.residual[0].weight, self.residual[1].weight, self.residual[1].bias
         else:
             wr = nrw = nrb = None
-        cfg = (self.kernel_size, self.stride, self.is_residual, self.normalization, self.compute_dtype,
-               active_sync(self))
+        cfg = LF.RtLayerCfg(Kt=self.kernel_size, S=self.stride, residual=self.is_residual, norm=self.normalization,
+                            dtype=self.compute_dtype, sync=active_sync(self))
         return LF.RtOfflineLayerFunction.apply(x, A_eff, self.conv.weight, self.conv.bias, n.weight, n.bias, wr,
                                                nrw, nrb, cfg)
 

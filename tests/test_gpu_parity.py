@@ -146,6 +146,42 @@ def test_layer_vs_oracle_larger(P, norm, cin, cout, stride):
         assert_grad_close(named[k].grad, g, TOL, k, grad_floor(grads, k), reduction=True)
 
 
+@pytest.mark.parametrize("cin,cout,stride", [(6, 6, 1), (6, 10, 2)])
+def test_layer_bn_nonfused_backward_vs_oracle(P, cin, cout, stride):
+    """A BatchNorm layer whose channel count is no multiple of 4 (fp32): bn_fused_ok is false, so norm2, norm1 and
+    the residual norm take the reduce / apply pair (layer_fn._norm_backward) instead of bn_bwd_fused.  fp32 HIP vs
+    the CPU oracle, forward and backward, at the fp32 layer tolerance; identity and conv residual."""
+    assert not P.native.bn_fused_ok(cout, torch.float32)
+    torch.manual_seed(11)
+    N, T = 2, 12
+    A = torch.tensor(P.Graph(**P.PKU_MMD).A, dtype=torch.float32)
+    layer = P.StgcnLayer(cin, cout, (9, 25), 3, 25, stride=stride, normalization="BatchNorm")
+    with torch.no_grad():
+        for name, p in layer.named_parameters():
+            if "tcn.0" in name or "tcn.3" in name or "residual.1" in name:
+                p.add_(0.1 * torch.randn(p.shape))
+    M = 1 + 0.1 * torch.randn(3, 25, 25)
+    x = torch.randn(N, cin, T, 25)
+    dy = torch.randn(N, cout, (T - 1) // stride + 1, 25)
+    sd = {k: v.clone().requires_grad_(True) for k, v in layer.state_dict().items()}
+    xr = x.clone().requires_grad_(True)
+    Ar = (A * M).requires_grad_(True)
+    ref = O.stgcn_layer(xr, Ar, sd, "", 9, stride, True, "BatchNorm")
+    ref.backward(dy)
+    layer = layer.to(DEV)
+    xg = x.to(DEV).requires_grad_(True)
+    Ag = (A * M).to(DEV).requires_grad_(True)
+    y = layer(xg, Ag)
+    y.backward(dy.to(DEV))
+    assert_close(y, ref, TOL, "y")
+    assert_grad_close(xg.grad, xr.grad, TOL, "dx")
+    assert_grad_close(Ag.grad, Ar.grad, TOL, "dA", reduction=True)
+    named = dict(layer.named_parameters())
+    grads = {k: v.grad for k, v in sd.items() if v.grad is not None}
+    for k, g in grads.items():
+        assert_grad_close(named[k].grad, g, TOL, k, grad_floor(grads, k), reduction=True)
+
+
 @pytest.mark.parametrize("cin,cout,stride", [(64, 64, 1), (64, 128, 2), (128, 64, 1)])
 def test_layer_bf16_vs_oracle(P, cin, cout, stride):
     """bf16 perf path of one BatchNorm layer at config-2 widths on the 25-joint graph vs the fp32 oracle: forward
