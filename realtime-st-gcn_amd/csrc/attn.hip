@@ -8,6 +8,7 @@
 // The score GEMM (K = T*ce, up to 4800) runs on MFMA with both operands loaded straight from the rows
 // (8 consecutive channels per lane = 16 B); blocks split T and add fp32 partials.
 #include "common.h"
+#include "launchers.h"
 
 void slab_sum_launch(const float* in, long B, long R, long E, float* tmp, float* out, int accumulate, hipStream_t s);
 long slab_sum_tmp_floats(long B, long R, long E);

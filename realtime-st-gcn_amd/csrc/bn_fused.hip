@@ -12,6 +12,7 @@
 // loads issued first (16-B units, channels-last), so every thread keeps several HBM requests in
 // flight; partial sums go to a workspace [blocks][C] and are folded in fp64 by a second kernel.
 #include "common.h"
+#include "launchers.h"
 #include "../../include/stgcn_amd.h"
 
 namespace {
@@ -295,10 +296,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_fused_kernel(const stgcn_bn_
 }
 
 // block target of the apply pass (the reduce pass keeps 1024: its partials are folded by sum4_kernel, and it
-// measured slower with fewer blocks); A/B build flag
-#ifndef STGCN_BN_APPLY_TB
-#define STGCN_BN_APPLY_TB 512
-#endif
+// measured slower with fewer blocks)
+constexpr long BN_APPLY_TB = 512;
 Geo geo(long M, int C, int vec, long tb = 1024) {
   Geo g;
   g.CU = C / vec;
@@ -324,7 +323,7 @@ bool fits(const stgcn_bn_bwd_desc& a, int dtype, int& vec) {
 }
 
 long bn_bwd_fused_work_floats_impl(long M, int C, int dtype) {
-  const Geo g = geo(M, C, dtype == 1 ? 8 : 4), ga = geo(M, C, dtype == 1 ? 8 : 4, STGCN_BN_APPLY_TB);
+  const Geo g = geo(M, C, dtype == 1 ? 8 : 4), ga = geo(M, C, dtype == 1 ? 8 : 4, BN_APPLY_TB);
   return (long)(g.nb > ga.nb ? g.nb : ga.nb) * C * 4;
 }
 
@@ -398,7 +397,7 @@ int bn_bwd_fused_apply_launch(const stgcn_bn_bwd_desc& a, int dtype, hipStream_t
   if (!fits(a, dtype, vec) || !a.out1 || !a.sums || !a.x1 || !a.mref || (a.osum && !a.work) || a.mask < 1 ||
       a.mask > 3)
     return STGCN_EBADSHAPE;
-  const Geo g = geo(a.M, a.C, vec, STGCN_BN_APPLY_TB);
+  const Geo g = geo(a.M, a.C, vec, BN_APPLY_TB);
   if (dtype == 1) apply_dispatch<bf16, 8>(a, g, s);
   else apply_dispatch<float, 4>(a, g, s);
   if (a.osum)

@@ -19,6 +19,7 @@
 // from the stored head, co_finish stores it.  Entry of age j lives in slot (head' + j) % fifo.
 // No floating-point atomics anywhere: a stream replays bit-identically.
 #include "common.h"
+#include "launchers.h"
 #include "frame_ops.h"
 #include "../../include/stgcn_amd.h"
 

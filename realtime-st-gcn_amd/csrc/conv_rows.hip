@@ -22,6 +22,7 @@
 // tap dt) pairs; A (gathered rows) and B (packed weights) tiles are double-buffered in LDS with
 // register prefetch of the next pair, XOR-swizzled so fragment reads are bank-conflict free.
 #include "common.h"
+#include "launchers.h"
 #include "pack.h"
 #include <stdlib.h>
 

@@ -12,6 +12,7 @@
 // Grid: x = m-range, y = tap dt, z = (co tile, ci tile); block tile 64(co) x 64(ci), 4 waves
 // each owning a 32x32 quadrant; K walked in 32-row steps, double-buffered.
 #include "common.h"
+#include "launchers.h"
 #include "lds_ops.h"
 #include "../../include/stgcn_amd.h"
 typedef stgcn_wgrad_desc WgradArgs;

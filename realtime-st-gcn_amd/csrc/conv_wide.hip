@@ -27,6 +27,7 @@
 //   * epilogue per tile: + bias, bf16 store, BatchNorm Welford partials per (tile, channel) (the
 //     float4 (count, mean, M2) layout bn_finalize merges; row-tile index = n * tiles_n + tile).
 #include "common.h"
+#include "launchers.h"
 #include "lds_ops.h"
 #include "pack.h"
 #include "../../include/stgcn_amd.h"

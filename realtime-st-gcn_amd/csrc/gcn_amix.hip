@@ -13,6 +13,7 @@
 // (K = P*Cin) runs on the MFMA row-conv kernel (conv_rows.hip).  amix_dA is a batched GEMM with
 // K = (t, ci) and both operands contiguous along ci, so it runs on MFMA straight from HBM.
 #include "common.h"
+#include "launchers.h"
 
 #include "../../include/stgcn_amd.h"
 typedef stgcn_amix_desc AmixArgs;

@@ -30,6 +30,7 @@
 // 8s+11 of the run) and 8 being written for step s+1; one block barrier per step hands them over.
 // Training forward: the kernel also writes g, u = z (pre-LN2), h and both LN statistics for the backward.
 #include "common.h"
+#include "launchers.h"
 #include "lds_ops.h"
 #include "../../include/stgcn_amd.h"
 #include <stdlib.h>

@@ -18,6 +18,7 @@
 //             summed over the blocks in a fixed order (deterministic; slab_sum_launch).
 // Bound: HBM (stats 1 read, apply 2-3 reads + 1 write, bwd 2-3 reads + 1 write of the activation).
 #include "common.h"
+#include "launchers.h"
 
 void slab_sum_launch(const float* in, long B, long R, long E, float* tmp, float* out, int accumulate, hipStream_t s);
 long slab_sum_tmp_floats(long B, long R, long E);

@@ -20,6 +20,7 @@
 // l, l+64, l+128, l+192 (C <= 256).  Sums are fixed-order (wave butterfly, then waves, then blocks):
 // bit-reproducible.
 #include "common.h"
+#include "launchers.h"
 
 namespace {
 

@@ -13,6 +13,7 @@
 // and recall float32 ratios of integer counts, F1 = 2 * P * R / (P + R) (NaN when the trial has no hit),
 // edit = 1 - D[m][n] / max(m, n).  Integer work is exact; the float results are bit-identical.
 #include "common.h"
+#include "launchers.h"
 
 namespace {
 

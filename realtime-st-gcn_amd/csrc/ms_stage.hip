@@ -23,6 +23,7 @@
 //                  prologue's Jacobian, or broadcast over the joints
 //   ms_prob      : the model's `out` selector (log-softmax | softmax over the classes) and its backward
 #include "common.h"
+#include "launchers.h"
 #include "../../include/stgcn_amd.h"
 
 namespace {

@@ -12,6 +12,7 @@
 //  Backward: dz = dy * relu-mask; BN: dx = g*rstd*(dz - E[dz] - xhat*E[dz*xhat]);
 //    LN: dx = rstd*(gz - mean(gz) - xhat*sum(gz*xhat)/(F-1)), gz = dz*gamma.
 #include "common.h"
+#include "launchers.h"
 #include <type_traits>
 
 namespace {

@@ -12,6 +12,7 @@
 // keeps it in CPU tensors, rtstgcn.py:576-579) and the indices in a device int[2], so the step can
 // be replayed from a HIP graph.
 #include "common.h"
+#include "launchers.h"
 
 namespace {
 

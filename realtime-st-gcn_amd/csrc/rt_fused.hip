@@ -18,6 +18,7 @@
 // Rows are channels-last [V][C] fp32 (the layout of the rest of the package); FIFO state [fifo][V][C],
 // accumulators [S][V][C], indices int[2] (fifo, acc) — device buffers, so a HIP graph can replay frames.
 #include "common.h"
+#include "launchers.h"
 #include "frame_ops.h"
 #include "../../include/stgcn_amd.h"
 
@@ -287,12 +288,9 @@ DEV float2 rf_block_sum2(float2 v, float* red) {  // two sums at once; red holds
   return t;
 }
 
-// output channels per task of the one-launch kernel (build flag for A/B: 4 channels, one task per workgroup at
-// G = 64 up to C = 256, measured 0.127 vs 0.109 ms/frame: the 12-row conv spills)
-#ifndef STGCN_RT_CB
-#define STGCN_RT_CB 2
-#endif
-constexpr int RF_CB = STGCN_RT_CB;
+// output channels per task of the one-launch kernel (4 channels, one task per workgroup at G = 64 up to C = 256,
+// measured 0.127 vs 0.109 ms/frame, not kept: the 12-row conv spills)
+constexpr int RF_CB = 2;
 // W rows of one channel-group task, staged in LDS: rows [0, P*RF_CB) = conv rows (p, cl) -> w[(p*Cout + co0 + cl)],
 // then RF_CB residual rows (res_mode 2); each thread moves at most RF_WU float4 units
 constexpr int RF_WROWS = PMAX * RF_CB + RF_CB;

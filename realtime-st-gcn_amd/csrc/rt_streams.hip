@@ -17,6 +17,7 @@
 // Every sum has a fixed order that depends on the network only: a stream's frames are bit-identical whatever B, its
 // slot and the other streams' masks are.
 #include "common.h"
+#include "launchers.h"
 #include "frame_ops.h"
 #include "../../include/stgcn_amd.h"
 

@@ -14,6 +14,7 @@
 // joints).  The data gradient of the 64-channel layers ships on this kernel; a frame-per-step form
 // for 25 < V <= 32 was removed in round 6 (no skeleton needs it).
 #include "common.h"
+#include "launchers.h"
 #include "lds_ops.h"
 #include "../../include/stgcn_amd.h"
 

@@ -11,6 +11,7 @@
 //   * per-block fp32 partials go to a slab, summed over the chunks in a fixed order (deterministic).
 // Served: bf16, M % 32 == 0, Cin and Cout multiples of 32, 16-B aligned rows; else the frame-tiled kernel.
 #include "common.h"
+#include "launchers.h"
 #include "lds_ops.h"
 #include "../../include/stgcn_amd.h"
 

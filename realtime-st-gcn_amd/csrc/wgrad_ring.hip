@@ -24,15 +24,9 @@
 //   * the fp32 block result goes to a slab [row range][9][Cout][Cin], summed in a fixed order by slab_reduce
 //     (wgrad_tile.hip): deterministic.
 #include "common.h"
+#include "launchers.h"
 #include "lds_ops.h"
 #include "../../include/stgcn_amd.h"
-
-#ifndef WR_G64
-#define WR_G64 2
-#endif
-#ifndef WR_D
-#define WR_D 2
-#endif
 
 namespace {
 
@@ -52,12 +46,8 @@ template <int G> struct Ring {
   static constexpr int YPANEL = YSLOT * KS * PR;             // bytes per 32-channel dY panel
 };
 // groups in flight: 2 (64 co: 120 KB of LDS, 128 co: 144 KB; 4 groups at 64 co measured slower, 79 vs 74 us)
-constexpr int ring_g(int cob) { return cob == 64 ? WR_G64 : 2; }
-constexpr size_t ring_lds(int cob) {
-  return ring_g(cob) == 4 ? 2 * (size_t)Ring<4>::XPANEL + (cob / 32) * (size_t)Ring<4>::YPANEL
-                          : ring_g(cob) == 3 ? 2 * (size_t)Ring<3>::XPANEL + (cob / 32) * (size_t)Ring<3>::YPANEL
-                                             : 2 * (size_t)Ring<2>::XPANEL + (cob / 32) * (size_t)Ring<2>::YPANEL;
-}
+constexpr int RING_G = 2;
+constexpr size_t ring_lds(int cob) { return 2 * (size_t)Ring<RING_G>::XPANEL + (cob / 32) * (size_t)Ring<RING_G>::YPANEL; }
 
 __device__ uint4 g_wr_zero[64];
 
@@ -84,7 +74,7 @@ struct WRGeom {
 // with a runtime V, most of them the 48 per-read address adds of a 64-co step)
 template <int COB, int PRO, int VT>
 __global__ __launch_bounds__(NT, 1) void wgrad_ring_kernel(const stgcn_wgrad_desc a, const WRGeom g) {
-  typedef Ring<ring_g(COB)> RG;
+  typedef Ring<RING_G> RG;
   constexpr int LOOK_X = RG::LOOK_X, LOOK_Y = RG::LOOK_Y, XSLOT = RG::XSLOT, YSLOT = RG::YSLOT;
   constexpr int XPANEL = RG::XPANEL, YPANEL = RG::YPANEL;
   constexpr int NYP = COB / 32;                 // dY panels
@@ -277,7 +267,7 @@ __global__ __launch_bounds__(NT, 1) void wgrad_ring_kernel(const stgcn_wgrad_des
     const char* Xl = sX + wi * XPANEL + ((s % XSLOT) * KS + t0 * V) * PR + loff;
     int tb = tapb;
     if constexpr (VT == 0) asm volatile("" : "+s"(tb));
-    constexpr int NU = 4 * TW, D = WR_D;  // fragments read D (ks, tap) steps ahead of their MFMA
+    constexpr int NU = 4 * TW, D = 2;  // fragments read D (ks, tap) steps ahead of their MFMA
     bf16x8 fx[D + 1], fy[2];
     auto rd = [&]<int u>() {
       constexpr int ks = u / TW, t = u % TW;

@@ -17,6 +17,7 @@
 // is reused by every tap), so the only output traffic is one fp32 partial per block: written to a
 // workspace slab with plain stores, then summed deterministically into dW by a second kernel.
 #include "common.h"
+#include "launchers.h"
 #include "lds_ops.h"
 #include <stdlib.h>
 #include "../../include/stgcn_amd.h"
@@ -223,23 +224,17 @@ __global__ __launch_bounds__(256, LN ? 1 : 2) void wgrad_tile_kernel(const stgcn
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-  // two tiles ahead: measured equal or slower here (config-2 step 8.037 vs 8.027 ms with one tile ahead, 3
-  // interleaved runs; the C = 64 wgrad's 2 blocks per CU already hide the loads), so off; the stride-2
-  // instantiations could not take it anyway (a second live set spills).  -DSTGCN_WT_AHEAD2=1: A/B builds.
-#ifndef STGCN_WT_AHEAD2
-#define STGCN_WT_AHEAD2 0
-#endif
-  constexpr bool AHEAD2 = STGCN_WT_AHEAD2 && S == 1;
+  // one tile ahead.  Two tiles ahead measured equal or slower here (config-2 step 8.037 vs 8.027 ms, 3 interleaved
+  // runs; the C = 64 wgrad's 2 blocks per CU already hide the loads), not kept; the stride-2 instantiations could
+  // not take it anyway (a second live set spills).
   const int nt = t_end - t_begin;
   if (nt > 0) {
     load.template operator()<0>(t_begin);
     store.template operator()<0>(0);
-    if constexpr (AHEAD2) load.template operator()<1>(t_begin + 1);
   }
   __syncthreads();
   auto tile = [&]<int SET>(int j) {  // tile j from LDS buffer j & 1 (= SET); tile j+1's loads go to set SET^1
-    if constexpr (AHEAD2) load.template operator()<SET>(t_begin + j + 2);
-    else load.template operator()<SET ^ 1>(t_begin + j + 1);
+    load.template operator()<SET ^ 1>(t_begin + j + 1);
     const char* sdy = smem + SET * STAGE;
     const char* sx = sdy + DY_BYTES;
 #pragma unroll 1

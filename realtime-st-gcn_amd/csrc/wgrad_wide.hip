@@ -23,6 +23,7 @@
 //   * the fp32 block result goes to a slab [range][9][Cout][Cin], summed deterministically into dW by
 //     slab_reduce (wgrad_tile.hip).
 #include "common.h"
+#include "launchers.h"
 #include "lds_ops.h"
 #include "../../include/stgcn_amd.h"
 #include <stdlib.h>

@@ -17,6 +17,7 @@
 // Layouts: capture fp32 [Cin][Lp][V] (batch 1, as the reference's trial loader gives it); activation rows
 // channels-last [nw][W][V][Cout] (bf16 or fp32), row stride ld.
 #include "common.h"
+#include "launchers.h"
 
 namespace {
 

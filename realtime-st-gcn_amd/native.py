@@ -664,7 +664,7 @@ def gconv_wgrad(x, dy, sup, Cin, Cout, rowsum=None):
 
 
 def gconv_wgrad3_shape(sup, Cin, Cout, dtype) -> bool:
-    """Whether stgcn_gconv_wgrad runs the DMA-ring kernel gconv_wgrad3 for this shape (gconv.hip w2_cob / w3_ok:
+    """Whether stgcn_gconv_wgrad runs the DMA-ring kernel gconv_wgrad3 for this shape (gconv_wgrad.hip plan_wgrad:
     bf16, channels % 64, <= 5 neighbours, not 64 -> 128)."""
     return dtype == torch.bfloat16 and Cin % 64 == 0 and Cout % 64 == 0 and sup.J <= 5 and not (Cin == 64 and Cout == 128)
 

@@ -44,6 +44,34 @@ def test_abi_rejects_bad_args_without_gpu(pkg):
     assert lib.stgcn_rt_frame(r, None) == 1
 
 
+# (plan, dtype, Cin, Cout, NT) -> workspace bytes (without, with row sums) at V = 25 and the PKU-MMD graph's J = 5:
+# one shape per plan of the graph-conv weight gradient.  The byte counts were recorded from the library as it was
+# before the plan moved into one function (gconv_wgrad.hip, plan_wgrad); they pin each shape's kernel family, row
+# parts and buffer layout.
+WGRAD_PLAN_BYTES = [
+    ("fp32", 0, 64, 64, 320, (0, 0)),
+    ("per-pair kernel", 1, 24, 40, 320, (1440000, 1440000)),
+    ("register-staged joint-grouped", 1, 64, 128, 320, (40960000, 41088000)),
+    ("ring with slab, 64 -> 64", 1, 64, 64, 320, (20480000, 20544000)),
+    ("ring with slab, 128 -> 256", 1, 128, 256, 320, (32768000, 32819200)),
+    ("ring direct split, 192 -> 256", 1, 192, 256, 320, (49306800, 49306800)),
+    ("ring direct split, 256 -> 128", 1, 256, 128, 14, (32871200, 32871200)),
+    ("wide, one row part", 1, 256, 256, 18, (0, 0)),
+    ("wide, two row parts", 1, 256, 256, 600, (78848800, 78848800)),
+]
+
+
+def test_gconv_wgrad_plan_workspace(pkg):
+    L = pkg._lib
+    lib = L.load_library()
+    sup = pkg.native.GraphSupport(torch.tensor(pkg.Graph(**pkg.PKU_MMD).A, dtype=torch.float32))
+    assert (sup.V, sup.J) == (25, 5)
+    for plan, dtype, Cin, Cout, NT, expect in WGRAD_PLAN_BYTES:
+        for rowsum, nbytes in zip((None, 16), expect):  # the size depends only on whether row sums are asked for
+            d = L.GconvWgradDesc(NT=NT, V=sup.V, J=sup.J, Cin=Cin, Cout=Cout, x_ld=Cin, dy_ld=Cout, rowsum=rowsum)
+            assert lib.stgcn_gconv_wgrad_workspace(d, dtype) == nbytes, (plan, bool(rowsum))
+
+
 @pytest.mark.parametrize("key,name", [("pku_mmd", "pku-mmd"), ("ntu_rgbpd", "ntu"), ("openpose", "op"),
                                       ("coco", "coco"), ("imu_fogit_ABCD", "imu"), ("hugadb", "hugadb")])
 def test_graph_golden(pkg, key, name):

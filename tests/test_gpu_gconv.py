@@ -145,6 +145,39 @@ def test_gconv_dgrad_masked_residual(K, pkg, Cin, Cout):
     assert torch.equal(out, ref)
 
 
+def test_gconv_wgrad_direct_split(K, pkg):
+    """The DMA-ring kernel's direct plan with both halves of a split joint non-empty: 192 -> 256 gives 300 channel
+    groups (one row part: the kernel writes dWeff and the row sums itself) and is not a 128 x 128 shape; NT = 70 is
+    3 row tiles, so the joints of degree >= 4 run as two blocks of 1 and 2 tiles that merge in-kernel.  Against
+    fp32 torch on the bf16-rounded inputs; the unused slots j >= deg[w] are exactly zero; twice, bit-equal (the
+    arrival counters are re-zeroed per launch)."""
+    torch.manual_seed(13)
+    Cin, Cout, N, T = 192, 256, 2, 35
+    A0 = torch.tensor(pkg.Graph(**pkg.PKU_MMD).A, dtype=torch.float32)
+    sup = K.GraphSupport(A0.to(DEV))
+    V, J = A0.shape[-1], sup.J
+    bf = torch.bfloat16
+    x, dy = torch.randn(N, Cin, T, V), torch.randn(N, Cout, T, V)
+    xr = x.to(bf).float().permute(0, 2, 3, 1).reshape(N * T, V, Cin)    # [i][v][ci]
+    dyr = dy.to(bf).float().permute(0, 2, 3, 1).reshape(N * T, V, Cout)
+    nbr, deg = sup.nbr.cpu(), sup.deg.cpu()
+    ref = torch.zeros(V, J, Cout, Cin)
+    for w in range(V):
+        for j in range(int(deg[w])):
+            ref[w, j] = dyr[:, w].t() @ xr[:, int(nbr[w, j])]
+    outs = []
+    for rep in range(2):
+        S = torch.empty((V, Cout), device=DEV)
+        outs.append((K.gconv_wgrad(cl(x, bf), cl(dy, bf), sup, Cin, Cout, rowsum=S), S))
+    torch.cuda.synchronize()
+    dweff, S = outs[0]
+    assert_close(dweff, ref, 2e-2, "dWeff direct split")
+    for w in range(V):
+        assert float(dweff[w, int(deg[w]):].abs().max() if int(deg[w]) < J else 0.0) == 0.0, w
+    assert_close(S.cpu(), dyr.sum(dim=0), 1e-4, "row sums direct split")
+    assert torch.equal(outs[1][0], dweff) and torch.equal(outs[1][1], S)
+
+
 @pytest.mark.parametrize("Cin,Cout,N,T", [(64, 64, 8, 40), (256, 256, 8, 75), (128, 256, 4, 60)])
 def test_gconv_wgrad_phases(K, pkg, Cin, Cout, N, T):
     """stgcn_gconv_wgrad split into its accumulation kernel (phase 1) and its slab reduction (phase 2) — what
