@@ -34,7 +34,8 @@ extern "C" {
  *   5: round 6 (stgcn_bn_merge: one (count, mean, M2) entry per channel, the SyncBatchNorm exchange unit);
  *   6: stgcn_co_* + stgcn_co_layer: CoST-GCN per-frame inference (co_frame.hip);
  *   7: stgcn_ms_* + stgcn_ms_layer / stgcn_ms_lin: MS-TCN stages, forward and backward (ms_stage.hip);
- *      still 7: stgcn_rt_streams* added (rt_streams.hip) — additive, no existing struct or entry point changed. */
+ *      still 7: stgcn_rt_streams* added (rt_streams.hip) — additive, no existing struct or entry point changed;
+ *      still 7: stgcn_co_streams* added (co_streams.hip) — additive likewise. */
 #define STGCN_ABI_VERSION 7
 
 /* Implicit-GEMM (Kt x 1) row convolution; see conv_rows.hip for the exact contract.
@@ -581,6 +582,66 @@ int stgcn_co_gcn(const stgcn_co_layer* d, void* stream);
 int stgcn_co_push(const stgcn_co_layer* d, void* stream);
 int stgcn_co_taps(const stgcn_co_layer* d, void* stream);
 int stgcn_co_finish(const stgcn_co_layer* d, void* stream);
+
+/* CoST-GCN per-frame inference for B independent streams (co_streams.hip): one call advances every active stream by one
+ * frame through the whole network.  Per stream the arithmetic is stgcn_co_layer's four stages (gcn, push, taps,
+ * finish) between an input head (LayerNorm([3,1,V]) + fcn_in) and an output head (mean over V + fcn_out); every
+ * hand-off is a kernel boundary, no atomics on floating-point data, no cooperative launch.
+ * State is stream-major and updated in place: ring [B][fifo][V][Cout] (dtype elements, fifo = S*(Kt-1)+1), res_ring
+ * [B][Kt/2+1][V][Cout] fp32, idx [B][2].  active [B] (device int32, read by the kernels): 0 = skip (the stream's state
+ * untouched, no ring reads, its out row written as zeros), 2 = restart then step (the kernels make every ring slot
+ * ReLU(ln1_b), the residual ring and idx zero, then push this frame: the caller need not initialise a stream it
+ * restarts), any other value = step.
+ * The tap stage runs groups of 4 active streams against one read of the weight panel (stgcn_co_pack_weight's image,
+ * unchanged); wp / wrp are stgcn_rt_streams_pack_weight's images of gcn.conv (groups = P, rows = Cout) and residual.0
+ * (groups = 1).  splits: 0 = the default, a function of (Cout, Kt) alone; stgcn_co_streams_splits returns the count
+ * used for layer l, stgcn_co_streams_workspace the bytes of that layer's `partial`.  With the same split counts a
+ * stream's outputs are bit-identical whatever B, its slot and the other streams' codes are.
+ * Limits per layer are stgcn_co_layer's (2 <= V <= 32, P <= 3, channels % 4 == 0 and <= 256, odd Kt <= 69, S in
+ * {1, 2}, res_mode 1 needs Cin == Cout), layers[l].Cin == layers[l-1].Cout (C0 for l = 0), 1 <= L <=
+ * STGCN_RT_MAX_LAYERS, B >= 1, K >= 1; dtype 0 fp32 | 1 bf16 (ring and wt only).  Anything else, or a NULL required
+ * pointer, returns 1 (2 for the dtype) before any launch; the two queries return -1. */
+typedef struct {
+  int Cin, Cout, P, Kt, S, res_mode, splits, pad_;
+  const float* A;       /* [P][V][V] graph * importance */
+  const float* wp;      /* packed gcn.conv weight, P * stgcn_rt_streams_pack_elems(Cout, Cin) floats */
+  const float* bias2d;  /* [V][Cout] or NULL */
+  const float* wrp;     /* packed residual.0 weight (res_mode 2) */
+  const float* br;      /* [Cout] or NULL */
+  const float* ln1_w;   /* tcn.0, (C,1,V) as stored */
+  const float* ln1_b;
+  const float* ln2_w;   /* tcn.3 */
+  const float* ln2_b;
+  const float* lnr_w;   /* residual.1 (res_mode 2) */
+  const float* lnr_b;
+  const void* wt;       /* packed tcn.2 weight, dtype elements */
+  const float* bt;      /* [Cout] tcn.2 bias or NULL */
+  void* ring;           /* [B][fifo][V][Cout] dtype elements */
+  float* res_ring;      /* [B][Kt/2+1][V][Cout] */
+  int* idx;             /* [B][2] */
+  float* z_buf;         /* [B][V][Cout] scratch */
+  float* r_buf;         /* [B][V][Cout] scratch (res_mode 2) */
+  float* partial;       /* [B][splits][V][Cout] scratch */
+  float* y;             /* [B][V][Cout] the layer's output rows */
+} stgcn_co_streams_layer;
+typedef struct {
+  int B, V, L, C0, K, dtype;
+  const float* x;       /* [B][3][V] */
+  const int* active;    /* [B] */
+  const float* ln_w;    /* [3*V] */
+  const float* ln_b;
+  const float* w_in;    /* [C0][3] */
+  const float* b_in;    /* [C0] */
+  const float* w_out;   /* [K][C_last] */
+  const float* b_out;   /* [K] or NULL */
+  float* h0;            /* [B][V][C0] scratch: the first layer's input rows */
+  int* order;           /* [B + 1] scratch: the active count, then the active streams' slots */
+  float* out;           /* [B][K] */
+  stgcn_co_streams_layer layers[STGCN_RT_MAX_LAYERS];
+} stgcn_co_streams_desc;
+int stgcn_co_streams_splits(const stgcn_co_streams_desc* d, int layer);
+long stgcn_co_streams_workspace(const stgcn_co_streams_desc* d, int layer);
+int stgcn_co_streams(const stgcn_co_streams_desc* d, void* stream);
 
 /* MS-TCN stage (models/mstcn/mstcn.py:68-116; ms_stage.hip): SingleStage = conv_in 1x1, num_layers
  * DilatedResidualLayers (dilation 2^i), conv_out 1x1, forward and backward, batch 1.  Activations are fp32 rows

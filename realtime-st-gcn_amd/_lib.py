@@ -121,6 +121,20 @@ class CoLayer(ctypes.Structure):  # stgcn_co_layer
                                         "partial", "y")]
 
 
+class CoStreamsLayer(ctypes.Structure):  # stgcn_co_streams_layer
+    _fields_ = [(n, c_int) for n in ("Cin", "Cout", "P", "Kt", "S", "res_mode", "splits", "pad_")] + \
+               [(n, c_void_p) for n in ("A", "wp", "bias2d", "wrp", "br", "ln1_w", "ln1_b", "ln2_w", "ln2_b", "lnr_w",
+                                        "lnr_b", "wt", "bt", "ring", "res_ring", "idx", "z_buf", "r_buf", "partial",
+                                        "y")]
+
+
+class CoStreamsDesc(ctypes.Structure):  # stgcn_co_streams_desc
+    _fields_ = [(n, c_int) for n in ("B", "V", "L", "C0", "K", "dtype")] + \
+               [(n, c_void_p) for n in ("x", "active", "ln_w", "ln_b", "w_in", "b_in", "w_out", "b_out", "h0", "order",
+                                        "out")] + \
+               [("layers", CoStreamsLayer * RT_MAX_LAYERS)]
+
+
 class MsLayer(ctypes.Structure):  # stgcn_ms_layer
     _fields_ = [(n, c_int) for n in ("R", "V", "F", "dil", "dtype", "pad_")] + \
                [(n, c_void_p) for n in ("x", "wp", "b1", "b2", "y", "h", "dy", "g", "dx", "part", "grads")]
@@ -222,6 +236,9 @@ _SIGS = {
     "stgcn_co_push": (c_int, [ctypes.POINTER(CoLayer), c_void_p]),
     "stgcn_co_taps": (c_int, [ctypes.POINTER(CoLayer), c_void_p]),
     "stgcn_co_finish": (c_int, [ctypes.POINTER(CoLayer), c_void_p]),
+    "stgcn_co_streams_splits": (c_int, [ctypes.POINTER(CoStreamsDesc), c_int]),
+    "stgcn_co_streams_workspace": (c_long, [ctypes.POINTER(CoStreamsDesc), c_int]),
+    "stgcn_co_streams": (c_int, [ctypes.POINTER(CoStreamsDesc), c_void_p]),
     "stgcn_ms_pack_elems": (c_long, [c_int]),
     "stgcn_ms_pack_layer": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
     "stgcn_ms_wgrad_blocks": (c_int, [c_int]),

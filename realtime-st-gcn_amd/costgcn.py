@@ -16,6 +16,9 @@ restarts the stream.  ``reset_state()`` restarts it explicitly and keeps the buf
 
 Scope: LayerNorm only (the reference's BatchNorm variant takes statistics over whatever the FIFO holds), batch 1,
 inference only, in_feat 3, V <= 32, P <= 3, channels % 4 == 0 and <= 256, odd Kt <= 69, stride 1 or 2.
+
+``Model.stream_batch(B)`` serves B independent streams per call (CoStreamBatch, co_streams.hip) with state of its own;
+``forward`` stays the call for one stream.
 """
 from __future__ import annotations
 
@@ -223,5 +226,148 @@ class Model(nn.Module):
                                f"{tuple(x.shape)}")
         return self._frame(x)
 
+    def stream_batch(self, B, splits=0):
+        """B independent skeleton streams of this model, advanced together one frame per call (CoStreamBatch,
+        stgcn_co_streams).  ``splits`` forces the tap stage's K-split count of every layer (0: the library's choice, a
+        function of the layer's shape alone).  The model's own single-stream state and forward are not touched."""
+        return CoStreamBatch(self, B, splits)
+
     def prepare_benchmark(self, arch_conf):
         return arch_conf
+
+
+class CoStreamBatch:
+    """B independent skeleton streams of one co-st-gcn (Model.stream_batch): every stream has its own activation
+    ring, residual ring and indices for every layer, and ``step`` advances the active ones by one frame
+    (stgcn_co_streams, co_streams.hip: the tap GEMM runs groups of streams against one read of the weights).  Follows
+    the model's ``compute_dtype``: fp32, or bf16 tap weights and rings.
+
+    The state buffers live here (``state``: per layer (ring, res_ring, idx); ``state_bytes`` / ``scratch_bytes``: what
+    was allocated) and survive a rebuild of the weight packs and the descriptor, which follows ``Model._key()``.  An
+    empty FIFO is ReLU(tcn.0.bias), so a parameter change makes the stream state stale: a rebuild restarts every
+    stream, as it does for the single-stream model."""
+
+    def __init__(self, model, B, splits=0):
+        if int(B) != B or B < 1:
+            raise RuntimeError(f"stgcn_amd: stream_batch needs B >= 1, got {B}")
+        K.L.require_device(model.A)
+        if model.fcn_in.in_channels != 3 or model.norm_in.weight.shape[0] != 3:
+            raise RuntimeError("stgcn_amd: co-st-gcn per-frame input head takes in_feat == 3")
+        if len(model.gcn_networks) > K.L.RT_MAX_LAYERS:
+            raise RuntimeError(f"stgcn_amd: co-st-gcn supports at most {K.L.RT_MAX_LAYERS} layers")
+        self.model, self.B, self.V, self.splits = model, int(B), model.A.shape[-1], int(splits)
+        self._all = torch.ones(self.B, dtype=torch.int32, device=model.A.device)
+        self.state, self._scratch, self._dtype, self._pack = [], None, None, None
+        self._desc()
+
+    # ------------------------------------------------------------------ buffers: once per (device, compute dtype)
+    def _shapes(self):
+        """The descriptor with B, the shapes and the split counts filled in; raises on unsupported shapes."""
+        m = self.model
+        d = K.L.CoStreamsDesc()
+        d.B, d.V, d.L, d.C0, d.K = self.B, self.V, len(m.gcn_networks), m.fcn_in.out_channels, m.fcn_out.out_channels
+        d.dtype = K.L.dtype_code(m.compute_dtype)
+        for i, l in enumerate(m.gcn_networks):
+            y = d.layers[i]
+            y.Cin, y.Cout, y.P, y.Kt, y.S = l.in_channels, l.out_channels, m.A.shape[0], l.gamma, l.stride
+            y.res_mode = 2 if l.is_residual_conv else (1 if l.is_residual else 0)
+            y.splits = self.splits
+        nbytes = []
+        for i in range(d.L):
+            d.layers[i].splits, nb = K.co_streams_workspace(d, i)
+            nbytes.append(nb)
+        return d, nbytes
+
+    def _alloc(self, d, nbytes):
+        m, B, V = self.model, self.B, self.V
+        dev, dt = m.A.device, m.compute_dtype
+        self.state, scratch = [], []
+        for i, l in enumerate(m.gcn_networks):
+            C = l.out_channels
+            self.state.append((torch.empty((B, l.fifo_size, V, C), dtype=dt, device=dev),
+                               torch.empty((B, l.gamma // 2 + 1, V, C), dtype=torch.float32, device=dev),
+                               torch.empty((B, 2), dtype=torch.int32, device=dev)))
+            scratch.append(dict(z=torch.empty((B, V, C), device=dev),
+                                r=torch.empty((B, V, C), device=dev) if l.is_residual_conv else None,
+                                partial=torch.empty(nbytes[i] // 4, device=dev),
+                                y=torch.empty((B, V, C), device=dev)))
+        self._scratch = dict(layers=scratch, h0=torch.empty((B, V, d.C0), device=dev),
+                             order=torch.zeros(B + 1, dtype=torch.int32, device=dev))
+        self._dtype = (dt, dev)
+        self.state_bytes = sum(t.numel() * t.element_size() for ts in self.state for t in ts)
+        self.scratch_bytes = sum(t.numel() * t.element_size() for sc in scratch for t in sc.values() if t is not None) \
+            + sum(self._scratch[k].numel() * 4 for k in ("h0", "order"))
+
+    def _desc(self):
+        m = self.model
+        key = m._key()
+        if self._pack is not None and self._pack[0] == key:
+            return self._pack[1]
+        with K.device_of(m.A):
+            d, nbytes = self._shapes()
+            if self._dtype != (m.compute_dtype, m.A.device):
+                self._alloc(d, nbytes)
+            V, P, dt, keep = self.V, m.A.shape[0], m.compute_dtype, []
+
+            def p(t):
+                keep.append(t)
+                return t.data_ptr()
+
+            def f32(t):
+                return t.detach().float().contiguous()
+
+            d.ln_w, d.ln_b = p(LF._flat_ln(m.norm_in.weight)), p(LF._flat_ln(m.norm_in.bias))
+            d.w_in, d.b_in = p(f32(m.fcn_in.weight).reshape(d.C0, -1)), p(f32(m.fcn_in.bias))
+            d.w_out, d.b_out = p(f32(m.fcn_out.weight).reshape(d.K, -1)), p(f32(m.fcn_out.bias))
+            d.h0, d.order = self._scratch["h0"].data_ptr(), self._scratch["order"].data_ptr()
+            for i, l in enumerate(m.gcn_networks):
+                C = l.out_channels
+                A_eff = f32(m.A * m.edge_importance[i])
+                y, sc = d.layers[i], self._scratch["layers"][i]
+                y.A = p(A_eff)
+                y.wp = p(K.rt_streams_pack_weight(l.gcn.conv.weight, P))
+                y.bias2d = p(K.gcn_bias(A_eff, f32(l.gcn.conv.bias), 1, C))
+                if l.is_residual_conv:
+                    y.wrp, y.br = p(K.rt_streams_pack_weight(l.residual[0].weight, 1)), p(f32(l.residual[0].bias))
+                    y.lnr_w, y.lnr_b = p(LF._flat_ln(l.residual[1].weight)), p(LF._flat_ln(l.residual[1].bias))
+                    y.r_buf = sc["r"].data_ptr()
+                y.ln1_w, y.ln1_b = p(LF._flat_ln(l.tcn[0].weight)), p(LF._flat_ln(l.tcn[0].bias))
+                y.ln2_w, y.ln2_b = p(LF._flat_ln(l.tcn[3].weight)), p(LF._flat_ln(l.tcn[3].bias))
+                y.wt, y.bt = p(K.co_pack_weight(l.tcn[2].weight, dt)), p(f32(l.tcn[2].bias))
+                y.ring, y.res_ring, y.idx = (t.data_ptr() for t in self.state[i])
+                y.z_buf, y.partial, y.y = sc["z"].data_ptr(), sc["partial"].data_ptr(), sc["y"].data_ptr()
+            self._pack = (key, (d, keep))
+            self.reset()  # the rings' empty content depends on tcn.0.bias: every stream restarts
+        return self._pack[1]
+
+    def step(self, x, active=None):
+        """x (B, 3, 1, V) -> (B, num_classes, 1).  ``active``: None (every stream steps), an int32 device tensor
+        [B] of codes (0 skip: state untouched, zero output row; 1 step; 2 restart then step) used as given with no
+        host sync, or a bool tensor / Python list converted on the host (True = step)."""
+        B, V = self.B, self.V
+        if x.dim() != 4 or tuple(x.shape) != (B, 3, 1, V):
+            raise RuntimeError(f"stgcn_amd: CoStreamBatch.step expects x of shape {(B, 3, 1, V)}, got {tuple(x.shape)}")
+        K.L.require_device(x)
+        x = K._f32c(x)
+        if active is None:
+            active = self._all
+        elif not (torch.is_tensor(active) and active.dtype == torch.int32 and active.is_cuda):
+            active = torch.as_tensor(active).to(device=x.device, dtype=torch.int32)
+        if tuple(active.shape) != (B,) or not active.is_contiguous():
+            raise RuntimeError(f"stgcn_amd: CoStreamBatch.step expects active of shape ({B},)")
+        d, _keep = self._desc()
+        out = torch.empty((B, d.K, 1), dtype=torch.float32, device=x.device)
+        with K.device_of(x):
+            return K.co_streams(d, x, active, out)
+
+    @torch.no_grad()
+    def reset(self, streams=None):
+        """Restart the given streams (an iterable of stream indices), or all of them: rings back to an empty FIFO
+        (ReLU(tcn.0.bias) / zero), indices cleared.  The buffers are kept, so a captured graph of a tick stays valid."""
+        sel = slice(None) if streams is None else torch.as_tensor(list(streams), dtype=torch.long,
+                                                                    device=self.model.A.device)
+        for l, (ring, res_ring, idx) in zip(self.model.gcn_networks, self.state):
+            b = torch.relu(l.tcn[0].bias.detach().float()).reshape(l.out_channels, self.V).t()
+            ring[sel] = b.to(ring.dtype)
+            res_ring[sel] = 0
+            idx[sel] = 0

@@ -76,38 +76,7 @@ __global__ __launch_bounds__(NT) void co_gcn_kernel(const float* __restrict__ x,
   }
 }
 
-// two-pass LayerNorm statistics (mean, 1 / sqrt(unbiased var + eps)) of the n = 4 * n4 values the block holds in
-// registers (unit e4 = tid + FNT * j), fixed-order sums
-DEV float2 ln_stats_reg(const float4 (&v)[U4], int n4, float* red) {
-  const int tid = threadIdx.x;
-  float s = 0.f;
-#pragma unroll
-  for (int j = 0; j < U4; ++j) s += tid + FNT * j < n4 ? sum4(v[j]) : 0.f;
-  const float n = 4.f * (float)n4;
-  const float mean = block_sum(s, red) / n;
-  float q = 0.f;
-#pragma unroll
-  for (int j = 0; j < U4; ++j) q += tid + FNT * j < n4 ? sq4(v[j], mean) : 0.f;
-  const float var = block_sum(q, red) / (n - 1.f);
-  return make_float2(mean, 1.f / sqrtf(var + 1e-5f));
-}
-
-// LayerNorm([C,1,V]) affine of the 4 elements of unit e4 of the rows [V][C]: parameter element c*V + v
-DEV float4 ln_apply4(float4 a, float2 st, const float* __restrict__ g, const float* __restrict__ b, int e4, int V,
-                     int C) {
-  const int e = e4 * 4, v = e / C, c = e - v * C;  // C % 4 == 0: one row
-  const int gi = c * V + v;
-  return make_float4(fmaf(g[gi], (a.x - st.x) * st.y, b[gi]), fmaf(g[gi + V], (a.y - st.x) * st.y, b[gi + V]),
-                     fmaf(g[gi + 2 * V], (a.z - st.x) * st.y, b[gi + 2 * V]),
-                     fmaf(g[gi + 3 * V], (a.w - st.x) * st.y, b[gi + 3 * V]));
-}
-
-DEV void store4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-DEV void store4(bf16* p, float4 v) {
-  bf16x4 o;
-  o[0] = (bf16)v.x, o[1] = (bf16)v.y, o[2] = (bf16)v.z, o[3] = (bf16)v.w;
-  *reinterpret_cast<bf16x4*>(p) = o;
-}
+DEV float2 ln_stats_reg(const float4 (&v)[U4], int n4, float* red) { return ln_stats_units<FNT>(v, n4, red); }
 
 template <typename T>
 __global__ __launch_bounds__(FNT) void co_push_kernel(const stgcn_co_layer d) {

@@ -1,4 +1,4 @@
-// Helpers of the per-frame (continual inference) kernels: rt_fused.hip, co_frame.hip and rt_streams.hip.
+// Helpers of the per-frame (continual inference) kernels: rt_fused.hip, co_frame.hip, rt_streams.hip and co_streams.hip.
 #pragma once
 #include "common.h"
 
@@ -54,4 +54,73 @@ DEV typename Tr<T>::frag load_b(const T* __restrict__ panel, int ks, int ks1, in
 #pragma unroll
   for (int j = 0; j < 8; ++j) b[j] = f[j];
   return b;
+}
+
+// two-pass LayerNorm statistics (mean, 1 / sqrt(unbiased var + eps)) of the n = 4 * n4 values a block of NTH threads
+// holds in registers (unit e4 = tid + NTH * j), fixed-order sums through red[NTH / 64]
+template <int NTH, int U>
+DEV float2 ln_stats_units(const float4 (&v)[U], int n4, float* red) {
+  const int tid = threadIdx.x;
+  float s = 0.f;
+#pragma unroll
+  for (int j = 0; j < U; ++j) s += tid + NTH * j < n4 ? sum4(v[j]) : 0.f;
+  const float n = 4.f * (float)n4;
+  const float mean = block_sum(s, red) / n;
+  float q = 0.f;
+#pragma unroll
+  for (int j = 0; j < U; ++j) q += tid + NTH * j < n4 ? sq4(v[j], mean) : 0.f;
+  const float var = block_sum(q, red) / (n - 1.f);
+  return make_float2(mean, 1.f / sqrtf(var + 1e-5f));
+}
+
+DEV float4 relu4(float4 v) { return make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)); }
+DEV float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+// w * (a - mean) * rstd + b per element
+DEV float4 affine4(float4 a, float mean, float rstd, float4 w, float4 b) {
+  return make_float4(fmaf(w.x, (a.x - mean) * rstd, b.x), fmaf(w.y, (a.y - mean) * rstd, b.y),
+                     fmaf(w.z, (a.z - mean) * rstd, b.z), fmaf(w.w, (a.w - mean) * rstd, b.w));
+}
+
+// The 4 parameter elements of a LayerNorm([C,1,V]) tensor (element c*V + v) that meet unit e4 of the rows [V][C]
+DEV float4 ln_param4(const float* __restrict__ p, int e4, int V, int C) {
+  const int e = e4 * 4, v = e / C, c = e - v * C;  // C % 4 == 0: one row
+  const int gi = c * V + v;
+  return make_float4(p[gi], p[gi + V], p[gi + 2 * V], p[gi + 3 * V]);
+}
+
+// LayerNorm([C,1,V]) affine of the 4 elements of unit e4 of the rows [V][C]: parameter element c*V + v
+DEV float4 ln_apply4(float4 a, float2 st, const float* __restrict__ g, const float* __restrict__ b, int e4, int V,
+                     int C) {
+  const int e = e4 * 4, v = e / C, c = e - v * C;  // C % 4 == 0: one row
+  const int gi = c * V + v;
+  return make_float4(fmaf(g[gi], (a.x - st.x) * st.y, b[gi]), fmaf(g[gi + V], (a.y - st.x) * st.y, b[gi + V]),
+                     fmaf(g[gi + 2 * V], (a.z - st.x) * st.y, b[gi + 2 * V]),
+                     fmaf(g[gi + 3 * V], (a.w - st.x) * st.y, b[gi + 3 * V]));
+}
+
+DEV void store4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
+DEV void store4(bf16* p, float4 v) {
+  bf16x4 o;
+  o[0] = (bf16)v.x, o[1] = (bf16)v.y, o[2] = (bf16)v.z, o[3] = (bf16)v.w;
+  *reinterpret_cast<bf16x4*>(p) = o;
+}
+
+// A fragment of k-step ks from fp32 rows in LDS (row stride ld): lane (row = l & 31, h = l >> 5) holds
+// x[row][16 ks + 8 h + j], j < 8; zero rows beyond V, zero beyond nks and Cin
+DEV f32x8 load_a(const float* xs, int ld, int ks, int nks, int row, int h, int V, int Cin) {
+  float f[8];
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const int kk = ks * 16 + 8 * h + 4 * u;
+    if (ks < nks && row < V && kk < Cin) {
+      load4(xs + row * ld + kk, f + 4 * u);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) f[4 * u + i] = 0.f;
+    }
+  }
+  f32x8 a;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) a[j] = f[j];
+  return a;
 }

@@ -128,6 +128,10 @@ int co_gcn_launch(const stgcn_co_layer& d, hipStream_t s);
 int co_push_launch(const stgcn_co_layer& d, hipStream_t s);
 int co_taps_launch(const stgcn_co_layer& d, hipStream_t s);
 int co_finish_launch(const stgcn_co_layer& d, hipStream_t s);
+// co_streams.hip
+int co_streams_check(const stgcn_co_streams_desc& d, bool shapes_only);
+int co_streams_num_splits(const stgcn_co_streams_desc& d, int layer);
+int co_streams_launch(const stgcn_co_streams_desc& d, hipStream_t s);
 // ms_stage.hip
 long ms_pack_elems(int F);
 int ms_pack_launch(const float* w1, const float* w2, int F, int kernel, void* dst, int dtype, hipStream_t s);

@@ -36,48 +36,7 @@ constexpr int XS_FLOATS = MAXE + VMAX * XPAD;
 // dynamic LDS (floats): xs | rs | zs[PMAX] | red
 constexpr int LDS_FLOATS = XS_FLOATS + MAXE + PMAX * MAXE + 16;
 
-// A fragment of k-step ks: lane (row = l & 31, h = l >> 5) holds x[row][16 ks + 8 h + j], j < 8; zero rows beyond V
-DEV f32x8 load_a(const float* xs, int ld, int ks, int nks, int row, int h, int V, int Cin) {
-  float f[8];
-#pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    const int kk = ks * 16 + 8 * h + 4 * u;
-    if (ks < nks && row < V && kk < Cin) {
-      load4(xs + row * ld + kk, f + 4 * u);
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) f[4 * u + i] = 0.f;
-    }
-  }
-  f32x8 a;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) a[j] = f[j];
-  return a;
-}
-
-DEV float4 relu4(float4 v) { return make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)); }
-DEV float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-// w * (a - mean) * rstd + b per element
-DEV float4 affine4(float4 a, float mean, float rstd, float4 w, float4 b) {
-  return make_float4(fmaf(w.x, (a.x - mean) * rstd, b.x), fmaf(w.y, (a.y - mean) * rstd, b.y),
-                     fmaf(w.z, (a.z - mean) * rstd, b.z), fmaf(w.w, (a.w - mean) * rstd, b.w));
-}
-
-// two-pass LayerNorm statistics (mean, 1 / sqrt(unbiased var + eps)) of the frame's n = 4 * n4 values in registers
-// (unit e4 = tid + NT * j)
-DEV float2 ln_stats_reg(const float4 (&v)[U4], int n4, float* red) {
-  const int tid = threadIdx.x;
-  float s = 0.f;
-#pragma unroll
-  for (int j = 0; j < U4; ++j) s += tid + NT * j < n4 ? sum4(v[j]) : 0.f;
-  const float n = 4.f * (float)n4;
-  const float mean = block_sum(s, red) / n;
-  float q = 0.f;
-#pragma unroll
-  for (int j = 0; j < U4; ++j) q += tid + NT * j < n4 ? sq4(v[j], mean) : 0.f;
-  const float var = block_sum(q, red) / (n - 1.f);
-  return make_float2(mean, 1.f / sqrtf(var + 1e-5f));
-}
+DEV float2 ln_stats_reg(const float4 (&v)[U4], int n4, float* red) { return ln_stats_units<NT>(v, n4, red); }
 
 __global__ __launch_bounds__(NT) void rt_streams_kernel(const stgcn_rt_streams_desc d) {
   extern __shared__ __attribute__((aligned(16))) float rs_sm[];

@@ -1073,6 +1073,25 @@ def co_layer_frame(desc):
     L.check(lib.stgcn_co_finish(d, s), "co_finish")
 
 
+def co_streams_workspace(desc, layer):
+    """(K-split count, bytes of the split partials) of layer ``layer`` of a stgcn_co_streams_desc (shapes and B
+    filled in); raises on shapes the kernels do not take."""
+    n = L.lib().stgcn_co_streams_splits(ctypes.byref(desc), layer)
+    nbytes = L.lib().stgcn_co_streams_workspace(ctypes.byref(desc), layer)
+    if n < 1 or nbytes < 0:
+        raise RuntimeError("stgcn_amd: co-st-gcn stream batch shape not supported (B >= 1, V <= 32, P <= 3, C % 4 == 0, "
+                           f"C <= 256, odd Kt <= 69, stride 1 or 2, at most {L.RT_MAX_LAYERS} layers)")
+    return n, nbytes
+
+
+def co_streams(desc, x, active, out):
+    """One frame of every active stream of a CoST-GCN stream batch (stgcn_co_streams): x (B, 3, 1, V) fp32 dense,
+    active (B) int32, out (B, K, 1); ``desc`` is the batch's stgcn_co_streams_desc (costgcn.CoStreamBatch)."""
+    desc.x, desc.active, desc.out = x.data_ptr(), active.data_ptr(), out.data_ptr()
+    L.check(L.lib().stgcn_co_streams(ctypes.byref(desc), L.stream()), "co_streams")
+    return out
+
+
 # ------------------------------------------------------------------------------ MS-TCN stage (ms_stage.hip)
 MS_MODES = {"logits": 0, "logsoftmax": 1, "softmax": 2}  # the `refine` / `output_type` selectors
 

@@ -23,12 +23,15 @@ ms:       MS-TCN refinement stage (F = 64, 10 layers, 52 classes, L = 2000; ms_s
           refinement stages; LossMultiStage, backward, Adam).  The plain-PyTorch restatement of the stage
           (tests/mstcn_ref.py) is timed on the host beside it.  Only with --only ms.
 
+co_streams: co-st-gcn as a stream batch (Model.stream_batch, stgcn_co_streams) at Kt in {9, 69} x {fp32, bf16} x
+          B in {1, 8, 64, 256}: one tick captured as a HIP graph, HIP-event device time over 200 replays after the
+          rings filled, beside the single-stream route graph-replayed in the same run.  Only with --only co_streams.
 streams:  config 3 as a stream batch (Model.stream_batch, stgcn_rt_streams): B in {1, 8, 64, 256, 1024} streams
           advanced one frame per launch, HIP-event device time over 200 graph-replayed ticks after the FIFOs have
           filled, beside the single-stream one-launch route (stgcn_rt_frame) graph-replayed in the same run: ms per
           tick, frames/s, and the ratio against B sequential single-stream replays.  Only with --only streams.
 
-    python tools/bench_configs.py [--frames 2000] [--steps 10] [--only 3|5|ln|f1|co|ms|streams]
+    python tools/bench_configs.py [--frames 2000] [--steps 10] [--only 3|5|ln|f1|co|ms|streams|co_streams]
 Prints one JSON line per config.
 """
 import argparse
@@ -410,6 +413,45 @@ def costgcn(P, dev, kernel, dtype, frames=256, cpu_frames=3):
             "reference_cited": "BASELINE.md: CoST-GCN per-frame 204 ms (Kt=9), 1.351 s (Kt=69)"}
 
 
+def co_streams(P, dev, kernel, dtype, batches=(1, 8, 64, 256)):
+    """Rows of the co-st-gcn stream-batch table: the reference schedule at temporal kernel ``kernel`` in ``dtype`` as
+    a stream batch (Model.stream_batch, stgcn_co_streams) of B streams, one tick captured as a HIP graph, beside the
+    single-stream route graph-replayed in the same run."""
+    arch = {"strategy": "spatial", "in_feat": 3, "stages": 1, "kernel": kernel, "output_type": "logits",
+            "normalization": "LayerNorm", "num_classes": 52, "graph": P.PKU_MMD,
+            "st-gcn": dict(LAYERS, kernel=kernel, latency=False, importance=True, in_feat=3, stages=1,
+                           dilation=[1] * 9)}
+    torch.manual_seed(0)
+    m = P.MODELS["co-st-gcn"](rank=None, **arch).to(dev).eval().set_compute_dtype(dtype)
+    fill = max(arch["st-gcn"]["stride"]) * (kernel - 1) + 1
+    gen = torch.Generator(device=dev).manual_seed(3)
+    es = 2 if dtype == "bf16" else 4
+    ring_bytes = sum(kernel * 25 * c * es for c in LAYERS["out_ch"])  # what one stream's tap stages read per tick
+    wbytes = sum(kernel * c * c * es for c in LAYERS["out_ch"])
+    rows = []
+    with torch.no_grad():
+        x1 = torch.randn(1, 3, 1, 25, device=dev, generator=gen)
+        single = _replay_ms(lambda: m(x1), fill)
+        for B in batches:
+            sb = m.stream_batch(B)
+            x = torch.randn(B, 3, 1, 25, device=dev, generator=gen)
+            ms = _replay_ms(lambda: sb.step(x), fill)
+            rows.append({"config": f"co-st-gcn as a stream batch (stgcn_co_streams), ln/costgcn_local.json widths, "
+                                   f"Kt={kernel}: B streams, one frame each per tick",
+                         "dtype": dtype, "Kt": kernel, "B": B, "tick_device_ms": round(ms, 4),
+                         "frames_per_s": round(B / ms * 1e3, 1), "single_stream_graph_device_ms": round(single, 4),
+                         "ratio_vs_B_sequential": round(ms / (B * single), 4),
+                         "k_splits": [sb._desc()[0].layers[i].splits for i in range(9)],
+                         "state_bytes_per_stream": sb.state_bytes // B,
+                         "ring_bytes_per_tick": B * ring_bytes,
+                         "tap_weight_bytes_per_tick": -(-B // 4) * wbytes,
+                         "ring_hbm_peak_fraction": round(B * ring_bytes / (ms * 1e-3) / HBM_PEAK_BPS, 4),
+                         "note": "HIP events around 200 graph replays after the rings filled; no per-kernel trace"})
+            del sb
+            torch.cuda.empty_cache()
+    return rows
+
+
 MS_TCN = {"latency": False, "importance": True, "stages": 3, "layers": [10, 10, 10], "kernel": [3, 3, 3],
           "filters": [64, 64, 64], "dropout": [0, 0, 0]}
 MSGCN_ARCH = {"strategy": "spatial", "receptive_field": 50, "segment": 2000, "in_feat": 3, "stages": 4,
@@ -549,6 +591,11 @@ def main():
     if args.only == "streams":
         for row in streams(P, dev):
             print(json.dumps(row), flush=True)
+    if args.only == "co_streams":
+        for kernel in (9, 69):
+            for dtype in ("fp32", "bf16"):
+                for row in co_streams(P, dev, kernel, dtype):
+                    print(json.dumps(row), flush=True)
     if args.only == "co":
         for kernel in (9, 69):
             for dtype in ("fp32", "bf16"):
