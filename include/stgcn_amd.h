@@ -35,7 +35,10 @@ extern "C" {
  *   6: stgcn_co_* + stgcn_co_layer: CoST-GCN per-frame inference (co_frame.hip);
  *   7: stgcn_ms_* + stgcn_ms_layer / stgcn_ms_lin: MS-TCN stages, forward and backward (ms_stage.hip);
  *      still 7: stgcn_rt_streams* added (rt_streams.hip) — additive, no existing struct or entry point changed;
- *      still 7: stgcn_co_streams* added (co_streams.hip) — additive likewise. */
+ *      still 7: stgcn_co_streams* added (co_streams.hip) — additive likewise;
+ *      still 7: stgcn_rt_streams_desc.pad_ became dtype (0 = fp32, what a zero-filled descriptor always passed; 1 = bf16
+ *      conv operands), stgcn_rt_streams_layer.wp / wrp became const void* of that element type, and
+ *      stgcn_rt_streams_pack_weight_as was added — no size, offset or existing entry point changed. */
 #define STGCN_ABI_VERSION 7
 
 /* Implicit-GEMM (Kt x 1) row convolution; see conv_rows.hip for the exact contract.
@@ -487,22 +490,29 @@ int stgcn_rt_frame(const stgcn_rt_frame_desc* d, void* stream);
  * atomics, no cooperative launch), so B may exceed the CU count.  The conv and the A-mix run on the fp32 matrix cores
  * (v_mfma_f32_32x32x2_f32, exact fp32 products, fixed summation order; LayerNorm statistics two-pass in a fixed
  * order): a stream's result does not depend on B, on its slot or on the other streams.
+ * dtype 1 (bf16 operands): the conv and the residual conv run on v_mfma_f32_32x32x16_bf16 with fp32 accumulation; the
+ * layer's input rows are rounded to bf16 (nearest even) as the A fragments are loaded and wp / wrp are bf16 images.
+ * Everything after the conv accumulators (A-mix, bias2d, FIFO step and state, LayerNorm, residual add, ReLU, the heads)
+ * is fp32 as with dtype 0, the identity residual reads the unrounded input, and the state buffers are the same.  Any
+ * other dtype returns 2 (unsupported dtype) before any launch.
  * State is stream-major and updated in place: fifo [B][fifo_size][V][Cout], acc [B][S][V][Cout], idx [B][2].
  * active [B] (device int32, read by the kernel): 0 = skip (state untouched, the out row written as zeros), 2 = restart
  * then step (FIFO, accumulators and indices taken as zero before this frame; the kernel clears them), any other
  * value = step.
  * wp: stgcn_rt_streams_pack_weight(w [P*Cout][Cin], groups = P, rows = Cout) — per partition the MFMA B-fragment image
  * [Cout/32 tiles][Cin/16 k-steps][64 lanes][8] of stgcn_co_pack_weight; wrp: the same of wr [Cout][Cin] (groups = 1),
- * res_mode 2 only.  The unpacked weights are not read.
+ * res_mode 2 only.  stgcn_rt_streams_pack_weight_as(..., dtype, ...) writes the same image in dtype (0: fp32, identical
+ * to stgcn_rt_streams_pack_weight; 1: bf16, rounded to nearest even); the element count is
+ * stgcn_rt_streams_pack_elems(rows, Cin) per group for both.  The unpacked weights are not read.
  * Limits of stgcn_rt_frame: 2 <= V <= 32, 4 <= C <= 256 (C % 4 == 0), V * C <= 7680, P <= 3, L <= STGCN_RT_MAX_LAYERS,
  * res_mode 1 needs Cin == Cout; B >= 1.  A NULL required pointer or a shape outside the limits returns 1 before any
  * launch. */
 typedef struct {
   int Cin, Cout, P, fifo_size, S, res_mode;
   const float* A;       /* [P][V][V] graph * importance */
-  const float* wp;      /* packed conv weight, P * stgcn_rt_streams_pack_elems(Cout, Cin) floats */
+  const void* wp;       /* packed conv weight, P * stgcn_rt_streams_pack_elems(Cout, Cin) elements of desc.dtype */
   const float* bias2d;  /* [V][Cout] or NULL */
-  const float* wrp;     /* packed residual conv weight (res_mode 2) or NULL */
+  const void* wrp;      /* packed residual conv weight (res_mode 2) of desc.dtype, or NULL */
   const float* ln_w;    /* [V][Cout], as stgcn_rt_layer */
   const float* ln_b;
   const float* lnr_w;   /* residual LN (res_mode 2), [V][Cout] */
@@ -512,7 +522,8 @@ typedef struct {
   int* idx;             /* [B][2] (fifo, acc) */
 } stgcn_rt_streams_layer;
 typedef struct {
-  int V, L, C0, K, B, pad_;
+  int V, L, C0, K, B;
+  int dtype;            /* conv operand type: 0 fp32, 1 bf16 (element type of every layer's wp / wrp) */
   const float* x;       /* [B][3][V] */
   const int* active;    /* [B] */
   const float* ln_w;    /* [3*V] */
@@ -526,6 +537,7 @@ typedef struct {
 } stgcn_rt_streams_desc;
 long stgcn_rt_streams_pack_elems(int rows, int Cin);
 int stgcn_rt_streams_pack_weight(const float* w, int groups, int rows, int Cin, float* dst, void* stream);
+int stgcn_rt_streams_pack_weight_as(const float* w, int groups, int rows, int Cin, void* dst, int dtype, void* stream);
 int stgcn_rt_streams(const stgcn_rt_streams_desc* d, void* stream);
 
 /* CoST-GCN per-frame inference (models/costgcn/costgcn.py:192-211; co_frame.hip), batch 1, one frame per call,

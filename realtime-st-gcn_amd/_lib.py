@@ -109,7 +109,7 @@ class RtStreamsLayer(ctypes.Structure):  # stgcn_rt_streams_layer
 
 
 class RtStreamsDesc(ctypes.Structure):  # stgcn_rt_streams_desc
-    _fields_ = [(n, c_int) for n in ("V", "L", "C0", "K", "B", "pad_")] + \
+    _fields_ = [(n, c_int) for n in ("V", "L", "C0", "K", "B", "dtype")] + \
                [(n, c_void_p) for n in ("x", "active", "ln_w", "ln_b", "w_in", "b_in", "w_out", "b_out", "out")] + \
                [("layers", RtStreamsLayer * RT_MAX_LAYERS)]
 
@@ -227,6 +227,7 @@ _SIGS = {
     "stgcn_rt_frame": (c_int, [ctypes.POINTER(RtFrameDesc), c_void_p]),
     "stgcn_rt_streams_pack_elems": (c_long, [c_int, c_int]),
     "stgcn_rt_streams_pack_weight": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "stgcn_rt_streams_pack_weight_as": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "stgcn_rt_streams": (c_int, [ctypes.POINTER(RtStreamsDesc), c_void_p]),
     "stgcn_co_pack_elems": (c_long, [c_int, c_int, c_int]),
     "stgcn_co_pack_weight": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),

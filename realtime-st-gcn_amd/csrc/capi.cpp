@@ -327,7 +327,10 @@ int stgcn_rt_frame(const stgcn_rt_frame_desc* d, void* stream) {
 
 long stgcn_rt_streams_pack_elems(int rows, int Cin) { return co_pack_rows_elems(rows, Cin); }
 int stgcn_rt_streams_pack_weight(const float* w, int groups, int rows, int Cin, float* dst, void* stream) {
-  return co_pack_rows_launch(w, groups, rows, Cin, dst, STREAM(stream));
+  return co_pack_rows_launch(w, groups, rows, Cin, dst, 0, STREAM(stream));
+}
+int stgcn_rt_streams_pack_weight_as(const float* w, int groups, int rows, int Cin, void* dst, int dtype, void* stream) {
+  return co_pack_rows_launch(w, groups, rows, Cin, dst, dtype, STREAM(stream));
 }
 int stgcn_rt_streams(const stgcn_rt_streams_desc* d, void* stream) {
   return d ? rt_streams_launch(*d, STREAM(stream)) : STGCN_EBADSHAPE;

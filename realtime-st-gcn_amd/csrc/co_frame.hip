@@ -297,18 +297,25 @@ int co_pack_launch(const float* w, int Cout, int C, int Kt, void* dst, int dtype
 
 // The same [tile][k-step][lane][8] image for `groups` consecutive row-major fp32 matrices [rows][C] (a 1x1 conv weight,
 // one group per partition; Kt = 1, so kk = ci): each group is packed on its own, so no 32-row tile straddles two groups.
+// dtype 0 fp32 | 1 bf16 (rounded to nearest even), the element count is the same.
 long co_pack_rows_elems(int rows, int C) {
   if (rows < 1 || rows > CMAX || C < 4 || C > CMAX || C % 4) return -1;
   return (long)((rows + 31) / 32) * num_ksteps(C, 1) * 512;
 }
 
-int co_pack_rows_launch(const float* w, int groups, int rows, int C, float* dst, hipStream_t s) {
+int co_pack_rows_launch(const float* w, int groups, int rows, int C, void* dst, int dtype, hipStream_t s) {
   const long total = co_pack_rows_elems(rows, C);
   if (!w || !dst || total < 0 || groups < 1 || groups > PMAX) return STGCN_EBADSHAPE;
+  if (dtype != 0 && dtype != 1) return STGCN_EDTYPE;
   const unsigned nb = (unsigned)((total + NT - 1) / NT);
-  for (int g = 0; g < groups; ++g)
-    hipLaunchKernelGGL(co_pack_kernel<float>, dim3(nb), dim3(NT), 0, s, w + (long)g * rows * C, rows, C, 1,
-                       num_ksteps(C, 1), total, dst + g * total);
+  for (int g = 0; g < groups; ++g) {
+    if (dtype == 0)
+      hipLaunchKernelGGL(co_pack_kernel<float>, dim3(nb), dim3(NT), 0, s, w + (long)g * rows * C, rows, C, 1,
+                         num_ksteps(C, 1), total, (float*)dst + g * total);
+    else
+      hipLaunchKernelGGL(co_pack_kernel<bf16>, dim3(nb), dim3(NT), 0, s, w + (long)g * rows * C, rows, C, 1,
+                         num_ksteps(C, 1), total, (bf16*)dst + g * total);
+  }
   return hipGetLastError() == hipSuccess ? STGCN_OK : STGCN_EHIP;
 }
 

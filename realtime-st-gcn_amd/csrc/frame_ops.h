@@ -124,3 +124,18 @@ DEV f32x8 load_a(const float* xs, int ld, int ks, int nks, int row, int h, int V
   for (int j = 0; j < 8; ++j) a[j] = f[j];
   return a;
 }
+
+// The same fragment as the MFMA operand type T: fp32 as read; bf16 rounded to nearest even here, once per staged
+// element, so the rows in LDS stay fp32 for whoever else reads them
+template <typename T>
+DEV typename Tr<T>::frag load_a_as(const float* xs, int ld, int ks, int nks, int row, int h, int V, int Cin) {
+  const f32x8 f = load_a(xs, ld, ks, nks, row, h, V, Cin);
+  if constexpr (sizeof(T) == 4) {
+    return f;
+  } else {
+    bf16x8 a;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) a[j] = (bf16)f[j];
+    return a;
+  }
+}

@@ -123,7 +123,7 @@ int co_num_splits(const stgcn_co_layer& d, hipStream_t s);
 long co_pack_elems(int Cout, int C, int Kt);
 int co_pack_launch(const float* w, int Cout, int C, int Kt, void* dst, int dtype, hipStream_t s);
 long co_pack_rows_elems(int rows, int C);
-int co_pack_rows_launch(const float* w, int groups, int rows, int C, float* dst, hipStream_t s);
+int co_pack_rows_launch(const float* w, int groups, int rows, int C, void* dst, int dtype, hipStream_t s);
 int co_gcn_launch(const stgcn_co_layer& d, hipStream_t s);
 int co_push_launch(const stgcn_co_layer& d, hipStream_t s);
 int co_taps_launch(const stgcn_co_layer& d, hipStream_t s);

@@ -1,13 +1,16 @@
-// RT-ST-GCN per-frame inference for a batch of B independent skeleton streams (stgcn_rt_streams), fp32, LayerNorm
-// online layers: one workgroup per stream runs the whole network for its stream's frame (rt_fused.hip's arithmetic:
+// RT-ST-GCN per-frame inference for a batch of B independent skeleton streams (stgcn_rt_streams), LayerNorm online
+// layers, conv operands fp32 or bf16 (template parameter T; all that follows the conv accumulators is fp32 in both): one workgroup per stream runs the whole network for its stream's frame (rt_fused.hip's arithmetic:
 // rt_in / rt_gcn / rt_norm / rt_out) with the layer input and output in LDS, the weights streamed from L2 (shared
 // by every workgroup) and the stream's FIFO state updated in place.  No workgroup waits on another: no grid barrier,
 // no spin, no atomics.  B may exceed the CU count; the workgroups queue.
 //
 // Per layer (V <= 32 joint rows, zero-padded to the 32-row MFMA operand by the fragment loads):
 //   (1) tasks over the 8 waves: (partition p, 32-channel tile) of the conv, and (tile) of the residual conv.
-//       Y_p[u][co] = sum_ci x[u][ci] W[p*Cout+co][ci]: v_mfma_f32_32x32x2_f32, A operand = x rows from LDS, B operand =
-//       the packed weight image (co_frame.hip's [tile][k-step][lane][8]: 32 B per lane per 16-k step, read once).
+//       Y_p[u][co] = sum_ci x[u][ci] W[p*Cout+co][ci]: v_mfma_f32_32x32x2_f32 (T = float) or v_mfma_f32_32x32x16_bf16
+//       (T = bf16), A operand = x rows from LDS, B operand = the packed weight image in T (co_frame.hip's
+//       [tile][k-step][lane][8]: one contiguous piece per lane per 16-k step, read once).  LDS keeps the rows in fp32
+//       only; the bf16 A fragment is rounded (nearest even) from them as it is loaded, so the identity residual and
+//       every later step read the unrounded values.
 //       The A-mix runs on the accumulators where they are: accumulator register r of lane l holds Y_p[acc_row(r, l)][co],
 //       which IS the B operand (k = l >> 5, n = l & 31) of an MFMA whose two k are u = acc_row(r, 0) and acc_row(r, 32);
 //       with A operand A_p[u][v] (m = v) sixteen MFMAs give Z_p[v][co] = sum_u A_p[u][v] Y_p[u][co].
@@ -38,6 +41,7 @@ constexpr int LDS_FLOATS = XS_FLOATS + MAXE + PMAX * MAXE + 16;
 
 DEV float2 ln_stats_reg(const float4 (&v)[U4], int n4, float* red) { return ln_stats_units<NT>(v, n4, red); }
 
+template <typename T>
 __global__ __launch_bounds__(NT) void rt_streams_kernel(const stgcn_rt_streams_desc d) {
   extern __shared__ __attribute__((aligned(16))) float rs_sm[];
   float* xs = rs_sm;            // [V][C + XPAD] the current layer's input
@@ -108,7 +112,8 @@ __global__ __launch_bounds__(NT) void rt_streams_kernel(const stgcn_rt_streams_d
         const bool res = task >= nconv;
         const int t2 = res ? task - nconv : task;
         const int p = res ? 0 : t2 / ntile, tile = res ? t2 : t2 - p * ntile;
-        const float* panel = (res ? ly.wrp : ly.wp + (long)p * ntile * nks * 512) + (long)tile * nks * 512;
+        const T* panel = res ? static_cast<const T*>(ly.wrp) : static_cast<const T*>(ly.wp) + (long)p * ntile * nks * 512;
+        panel += (long)tile * nks * 512;
         float am[16];  // A_p[u = acc_row(r, lane)][v = row]
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -119,13 +124,13 @@ __global__ __launch_bounds__(NT) void rt_streams_kernel(const stgcn_rt_streams_d
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = 0.f;
         for (int kb = 0; kb < nks; kb += TU) {
-          f32x8 fa[TU], fb[TU];
+          typename Tr<T>::frag fa[TU], fb[TU];
 #pragma unroll
-          for (int u = 0; u < TU; ++u) fb[u] = load_b<float>(panel, kb + u, nks, lane);
+          for (int u = 0; u < TU; ++u) fb[u] = load_b<T>(panel, kb + u, nks, lane);
 #pragma unroll
-          for (int u = 0; u < TU; ++u) fa[u] = load_a(xs, ldx, kb + u, nks, row, h, V, Cin);
+          for (int u = 0; u < TU; ++u) fa[u] = load_a_as<T>(xs, ldx, kb + u, nks, row, h, V, Cin);
 #pragma unroll
-          for (int u = 0; u < TU; ++u) Tr<float>::mma(acc, fa[u], fb[u]);
+          for (int u = 0; u < TU; ++u) Tr<T>::mma(acc, fa[u], fb[u]);
         }
         float* dst = rs;
         if (!res) {
@@ -218,6 +223,14 @@ __global__ __launch_bounds__(NT) void rt_streams_kernel(const stgcn_rt_streams_d
   }
 }
 
+template <typename T>
+int launch_as(const stgcn_rt_streams_desc& d, hipStream_t s) {
+  constexpr int lds = LDS_FLOATS * (int)sizeof(float);
+  if (stgcn_lds_attr((const void*)rt_streams_kernel<T>, lds, s)) return STGCN_EHIP;
+  hipLaunchKernelGGL(rt_streams_kernel<T>, dim3((unsigned)d.B), dim3(NT), lds, s, d);
+  return hipGetLastError() == hipSuccess ? STGCN_OK : STGCN_EHIP;
+}
+
 }  // namespace
 
 int rt_streams_launch(const stgcn_rt_streams_desc& d, hipStream_t s) {
@@ -225,6 +238,7 @@ int rt_streams_launch(const stgcn_rt_streams_desc& d, hipStream_t s) {
   if (d.V < 2 || d.V > VMAX || d.L < 1 || d.L > STGCN_RT_MAX_LAYERS || d.C0 < 4 || d.C0 > CMAX || d.C0 % 4 ||
       d.V * d.C0 > MAXE || d.K < 1 || d.B < 1)
     return STGCN_EBADSHAPE;
+  if (d.dtype != 0 && d.dtype != 1) return STGCN_EDTYPE;
   int cin = d.C0;
   for (int l = 0; l < d.L; ++l) {
     const stgcn_rt_streams_layer& y = d.layers[l];
@@ -236,8 +250,5 @@ int rt_streams_launch(const stgcn_rt_streams_desc& d, hipStream_t s) {
       return STGCN_EBADSHAPE;
     cin = y.Cout;
   }
-  constexpr int lds = LDS_FLOATS * (int)sizeof(float);
-  if (stgcn_lds_attr((const void*)rt_streams_kernel, lds, s)) return STGCN_EHIP;
-  hipLaunchKernelGGL(rt_streams_kernel, dim3((unsigned)d.B), dim3(NT), lds, s, d);
-  return hipGetLastError() == hipSuccess ? STGCN_OK : STGCN_EHIP;
+  return d.dtype == 0 ? launch_as<float>(d, s) : launch_as<bf16>(d, s);
 }

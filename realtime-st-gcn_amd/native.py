@@ -1017,18 +1017,20 @@ def rt_frame(desc, x, out):
     return out
 
 
-def rt_streams_pack_weight(w, groups):
-    """``groups`` stacked 1x1-conv weights (groups * rows, Cin) -> rt_streams.hip's MFMA B-fragment image (fp32),
-    one [rows/32 tiles][Cin/16 k-steps][64 lanes][8] panel set per group."""
+def rt_streams_pack_weight(w, groups, dtype=torch.float32):
+    """``groups`` stacked 1x1-conv weights (groups * rows, Cin) -> rt_streams.hip's MFMA B-fragment image in
+    ``dtype`` (fp32, or bf16 rounded to nearest even), one [rows/32 tiles][Cin/16 k-steps][64 lanes][8] panel set per
+    group."""
+    code = L.dtype_code(dtype)
     L.require_device(w)
     w = _f32c(w.detach().reshape(w.shape[0], -1))
     rows, Cin = w.shape[0] // groups, w.shape[1]
     n = L.lib().stgcn_rt_streams_pack_elems(rows, Cin)
     if n < 0 or rows * groups != w.shape[0]:
         raise RuntimeError(f"stgcn_amd: rt_streams_pack_weight: unsupported shape rows={rows} Cin={Cin}")
-    out = torch.empty(groups * n, dtype=torch.float32, device=w.device)
-    L.check(L.lib().stgcn_rt_streams_pack_weight(w.data_ptr(), groups, rows, Cin, out.data_ptr(), L.stream()),
-            "rt_streams_pack_weight")
+    out = torch.empty(groups * n, dtype=dtype, device=w.device)
+    L.check(L.lib().stgcn_rt_streams_pack_weight_as(w.data_ptr(), groups, rows, Cin, out.data_ptr(), code,
+                                                    L.stream()), "rt_streams_pack_weight")
     return out
 
 

@@ -361,11 +361,16 @@ class Model(nn.Module):
                 y.r_buf = p(torch.empty(V * Cout, dtype=torch.float32, device=dev))
         return d, keep
 
-    def stream_batch(self, B):
+    def stream_batch(self, B, dtype=None):
         """B independent skeleton streams of this online model, advanced together one frame per launch
         (RtStreamBatch, stgcn_rt_streams).  Valid after prepare_benchmark; the model's own single-stream state and
-        forward are not touched."""
-        return RtStreamBatch(self, B)
+        forward are not touched.
+
+        ``dtype`` is the operand type of the layers' 1x1 convs: None or "fp32" / torch.float32 (exact fp32 products),
+        or "bf16" / torch.bfloat16 (inputs and weights rounded to bf16 for the matrix cores, fp32 accumulation;
+        state, A-mix, LayerNorm, residual and the heads stay fp32).  The online form is fp32 unless asked for here:
+        set_compute_dtype does not change what stream_batch(B) returns."""
+        return RtStreamBatch(self, B, dtype)
 
     def _swap_layers_for_inference(self):
         """Replace OfflineLayers by OnlineLayers carrying the same parameters (rtstgcn.py:160-187)."""
@@ -393,12 +398,19 @@ class Model(nn.Module):
 class RtStreamBatch:
     """B independent skeleton streams of one online LayerNorm rt-st-gcn (Model.stream_batch): every stream has its
     own FIFO, accumulators and indices for every layer, and ``step`` advances all of them by one frame in one launch
-    (stgcn_rt_streams, rt_streams.hip: one workgroup per stream, no communication between workgroups).  fp32.
+    (stgcn_rt_streams, rt_streams.hip: one workgroup per stream, no communication between workgroups).  ``dtype``
+    (torch.float32, the default, or torch.bfloat16) is the operand type of the conv MFMAs and of the packed weight
+    images the batch holds; state and outputs are fp32 either way.
 
     The state buffers live here and survive a rebuild of the descriptor (which follows the parameters' data
     pointers and in-place versions, as Model._frame_key does); the model's own single-stream state is not used."""
 
-    def __init__(self, model, B):
+    def __init__(self, model, B, dtype=None):
+        try:
+            self.dtype = torch.float32 if dtype is None else resolve_dtype(dtype)
+        except (KeyError, TypeError):
+            raise RuntimeError(f"stgcn_amd: stream_batch supports dtype fp32 (torch.float32) or bf16 "
+                               f"(torch.bfloat16), got {dtype!r}") from None
         if not model.online:
             raise RuntimeError("stgcn_amd: stream_batch needs the online layers: call prepare_benchmark first")
         if model.normalization != "LayerNorm":
@@ -421,6 +433,7 @@ class RtStreamBatch:
             self.state.append((torch.zeros(self.B, ag.fifo_size, V, ag.out_channels, device=dev),
                                torch.zeros(self.B, ag.stride, V, ag.out_channels, device=dev),
                                torch.zeros(self.B, 2, dtype=torch.int32, device=dev)))
+        self.state_bytes = sum(t.numel() * t.element_size() for ts in self.state for t in ts)  # fp32 whatever dtype
         self._all = torch.ones(self.B, dtype=torch.int32, device=dev)
         self._pack = None
 
@@ -437,6 +450,7 @@ class RtStreamBatch:
 
         d = K.L.RtStreamsDesc()
         d.V, d.L, d.C0, d.K, d.B = V, len(m.st_gcn), m.fcn_in.out_channels, m.fcn_out.out_channels, self.B
+        d.dtype = K.L.dtype_code(self.dtype)
         d.ln_w, d.ln_b = p(LF._flat_ln(m.norm_in.weight)), p(LF._flat_ln(m.norm_in.bias))
         d.w_in = p(m.fcn_in.weight.detach().float().reshape(d.C0, -1).contiguous())
         d.b_in = p(m.fcn_in.bias.detach().float().contiguous())
@@ -450,7 +464,7 @@ class RtStreamBatch:
             y.Cin, y.Cout, y.P, y.fifo_size, y.S = Cin, Cout, P, ag.fifo_size, ag.stride
             y.res_mode = 2 if l.is_residual_conv else (1 if l.is_residual else 0)
             y.A, y.bias2d = p(A32), p(bias2d)
-            y.wp = p(K.rt_streams_pack_weight(l.conv.weight, P))
+            y.wp = p(K.rt_streams_pack_weight(l.conv.weight, P, self.dtype))
 
             def rows(t):  # LayerNorm([C,1,V]) affine (C,1,V) -> the rows' [V][C] layout
                 return t.detach().float().reshape(Cout, V).t().contiguous()
@@ -458,7 +472,7 @@ class RtStreamBatch:
             n = l.bn_relu[0]
             y.ln_w, y.ln_b = p(rows(n.weight)), p(rows(n.bias))
             if l.is_residual_conv:
-                y.wrp = p(K.rt_streams_pack_weight(l.residual[0].weight, 1))
+                y.wrp = p(K.rt_streams_pack_weight(l.residual[0].weight, 1, self.dtype))
                 y.lnr_w, y.lnr_b = p(rows(l.residual[1].weight)), p(rows(l.residual[1].bias))
             y.fifo, y.acc, y.idx = (t.data_ptr() for t in self.state[i])
         self._pack = (key, (d, keep))

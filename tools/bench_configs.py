@@ -29,7 +29,9 @@ co_streams: co-st-gcn as a stream batch (Model.stream_batch, stgcn_co_streams) a
 streams:  config 3 as a stream batch (Model.stream_batch, stgcn_rt_streams): B in {1, 8, 64, 256, 1024} streams
           advanced one frame per launch, HIP-event device time over 200 graph-replayed ticks after the FIFOs have
           filled, beside the single-stream one-launch route (stgcn_rt_frame) graph-replayed in the same run: ms per
-          tick, frames/s, and the ratio against B sequential single-stream replays.  Only with --only streams.
+          tick, frames/s, and the ratio against B sequential single-stream replays.  Both operand types (fp32,
+          bf16) are measured in the same process, interleaved per B, --stream-repeats times over; the rows are also
+          appended to profiles/rt_streams.jsonl.  Only with --only streams.
 
     python tools/bench_configs.py [--frames 2000] [--steps 10] [--only 3|5|ln|f1|co|ms|streams|co_streams]
 Prints one JSON line per config.
@@ -189,7 +191,7 @@ def _replay_ms(step, fill, reps=200):
     return e0.elapsed_time(e1) / reps
 
 
-def streams(P, dev, batches=(1, 8, 64, 256, 1024)):
+def streams(P, dev, batches=(1, 8, 64, 256, 1024), repeats=1):
     torch.manual_seed(0)
     m = P.MODELS["rt-st-gcn"](rank=None, **dict(RT_ARCH, graph=P.PKU_MMD)).to(dev)
     m.eval()
@@ -206,15 +208,18 @@ def streams(P, dev, batches=(1, 8, 64, 256, 1024)):
             single = _replay_ms(lambda: m(x1), fill)
         finally:
             R.rt_one_launch = prev
-        for B in batches:
-            sb = m.stream_batch(B)
-            x = torch.randn(B, 3, 1, 25, device=dev, generator=gen)
-            ms = _replay_ms(lambda: sb.step(x), fill)
-            rows.append({"config": "3 as a stream batch (stgcn_rt_streams): B streams, one frame each per launch",
-                         "dtype": "fp32", "B": B, "tick_device_ms": round(ms, 4),
-                         "frames_per_s": round(B / ms * 1e3, 1),
-                         "single_stream_one_launch_device_ms": round(single, 4),
-                         "ratio_vs_B_sequential": round(ms / (B * single), 4)})
+        for r in range(repeats):
+            for B in batches:
+                x = torch.randn(B, 3, 1, 25, device=dev, generator=gen)
+                for dtype in ("fp32", "bf16"):  # interleaved: the two operand types see the same device state
+                    sb = None  # the previous batch's state is freed before the next one is allocated
+                    sb = m.stream_batch(B, dtype)
+                    ms = _replay_ms(lambda: sb.step(x), fill)
+                    rows.append({"config": "3 as a stream batch (stgcn_rt_streams): B streams, one frame each per "
+                                           "launch", "dtype": dtype, "B": B, "repeat": r,
+                                 "tick_device_ms": round(ms, 4), "frames_per_s": round(B / ms * 1e3, 1),
+                                 "single_stream_one_launch_device_ms": round(single, 4),
+                                 "ratio_vs_B_sequential": round(ms / (B * single), 4)})
     return rows
 
 
@@ -571,6 +576,7 @@ def main():
     ap.add_argument("--only", default=None)
     ap.add_argument("--ln-reps", type=int, default=3)
     ap.add_argument("--ln-route", choices=("both", "fused", "unfused"), default="both")
+    ap.add_argument("--stream-repeats", type=int, default=3)
     args = ap.parse_args()
     P = ge.load_package()
     dev = torch.device("cuda", 0)
@@ -589,8 +595,10 @@ def main():
         for dtype in ("fp32", "bf16"):
             print(json.dumps(msgcn_step(P, dev, dtype, min(args.steps, 5))), flush=True)
     if args.only == "streams":
-        for row in streams(P, dev):
-            print(json.dumps(row), flush=True)
+        with open(os.path.join(ROOT, "profiles", "rt_streams.jsonl"), "a") as f:
+            for row in streams(P, dev, repeats=args.stream_repeats):
+                print(json.dumps(row), flush=True)
+                f.write(json.dumps(row) + "\n")
     if args.only == "co_streams":
         for kernel in (9, 69):
             for dtype in ("fp32", "bf16"):
