@@ -29,6 +29,7 @@ from . import layer_fn as LF
 from . import native as K
 from .graph import Graph
 from .modules import ConvTemporalGraphical, LayerNorm, resolve_dtype
+from .streams import Keep, StreamBatch, f32, fill_heads, res_mode_of
 
 
 class CoStgcnLayer(nn.Module):
@@ -60,6 +61,25 @@ class CoStgcnLayer(nn.Module):
                                           LayerNorm([out_channels, 1, num_joints]))
         else:
             self.residual = nn.Identity()
+
+
+def empty_ring_row(l, V):
+    """An empty FIFO as the activation ring caches it: ReLU(LN1(0)) = ReLU(tcn.0.bias), rows [V][C] fp32."""
+    return torch.relu(l.tcn[0].bias.detach().float()).reshape(l.out_channels, V).t()
+
+
+def _fill_layer(y, l, A_eff, keep, dt):
+    """The fields stgcn_co_layer and stgcn_co_streams_layer both carry, from layer ``l`` (``A_eff`` = A * importance,
+    ``dt`` the tap weights' dtype); the caller adds its conv weights (raw or packed) and its buffers."""
+    C = l.out_channels
+    y.A = keep(A_eff)
+    y.bias2d = keep(K.gcn_bias(A_eff, f32(l.gcn.conv.bias), 1, C))
+    if l.is_residual_conv:
+        y.br = keep(f32(l.residual[0].bias))
+        y.lnr_w, y.lnr_b = keep(LF._flat_ln(l.residual[1].weight)), keep(LF._flat_ln(l.residual[1].bias))
+    y.ln1_w, y.ln1_b = keep(LF._flat_ln(l.tcn[0].weight)), keep(LF._flat_ln(l.tcn[0].bias))
+    y.ln2_w, y.ln2_b = keep(LF._flat_ln(l.tcn[3].weight)), keep(LF._flat_ln(l.tcn[3].bias))
+    y.wt, y.bt = keep(K.co_pack_weight(l.tcn[2].weight, dt)), keep(f32(l.tcn[2].bias))
 
 
 class Model(nn.Module):
@@ -128,9 +148,7 @@ class Model(nn.Module):
 
     def _ring_init(self, layer, ring, res_ring, idx):
         """An empty FIFO as the ring caches it: ReLU(LN1(0)) = ReLU(tcn.0.bias) in every slot; residuals zero."""
-        V, C = self.A.shape[-1], layer.out_channels
-        b = torch.relu(layer.tcn[0].bias.detach().float()).reshape(C, V).t()
-        ring.copy_(b.unsqueeze(0).expand_as(ring))
+        ring.copy_(empty_ring_row(layer, self.A.shape[-1]).unsqueeze(0).expand_as(ring))
         res_ring.zero_()
         idx.zero_()
 
@@ -142,34 +160,21 @@ class Model(nn.Module):
             raise RuntimeError(f"stgcn_amd: co-st-gcn supports at most {K.L.RT_MAX_LAYERS} layers")
         if self.fcn_in.in_channels != 3 or self.norm_in.weight.shape[0] != 3:
             raise RuntimeError("stgcn_amd: co-st-gcn per-frame input head takes in_feat == 3")
-        keep, descs, state = [], [], []
-
-        def p(t):
-            keep.append(t)
-            return t.data_ptr()
-
-        def f32(t):
-            return t.detach().float().contiguous()
-
+        p = keep = Keep()
+        descs, state = [], []
         for i, l in enumerate(self.gcn_networks):
             Cin, C, Kt = l.in_channels, l.out_channels, l.gamma
             A_eff = f32(self.A * self.edge_importance[i])
             d = K.L.CoLayer()
             d.V, d.Cin, d.Cout, d.P, d.Kt, d.S = V, Cin, C, P, Kt, l.stride
-            d.res_mode = 2 if l.is_residual_conv else (1 if l.is_residual else 0)
+            d.res_mode = res_mode_of(l)
             d.dtype, d.splits = K.L.dtype_code(dt), self.k_splits
             d.splits, nbytes = K.co_workspace(d)  # raises on shapes the kernels do not take
-            d.A = p(A_eff)
+            _fill_layer(d, l, A_eff, keep, dt)
             d.w = p(f32(l.gcn.conv.weight).reshape(P * C, Cin))
-            d.bias2d = p(K.gcn_bias(A_eff, f32(l.gcn.conv.bias), 1, C))
             if l.is_residual_conv:
-                d.wr, d.br = p(f32(l.residual[0].weight).reshape(C, Cin)), p(f32(l.residual[0].bias))
-                d.lnr_w, d.lnr_b = p(LF._flat_ln(l.residual[1].weight)), p(LF._flat_ln(l.residual[1].bias))
+                d.wr = p(f32(l.residual[0].weight).reshape(C, Cin))
                 d.r_buf = p(torch.empty(V * C, dtype=torch.float32, device=dev))
-            d.ln1_w, d.ln1_b = p(LF._flat_ln(l.tcn[0].weight)), p(LF._flat_ln(l.tcn[0].bias))
-            d.ln2_w, d.ln2_b = p(LF._flat_ln(l.tcn[3].weight)), p(LF._flat_ln(l.tcn[3].bias))
-            d.wt = p(K.co_pack_weight(l.tcn[2].weight, dt))
-            d.bt = p(f32(l.tcn[2].bias))
             ring = torch.empty((l.fifo_size, V, C), dtype=dt, device=dev)
             res_ring = torch.empty((Kt // 2 + 1, V, C), dtype=torch.float32, device=dev)
             idx = torch.empty(2, dtype=torch.int32, device=dev)
@@ -236,7 +241,7 @@ class Model(nn.Module):
         return arch_conf
 
 
-class CoStreamBatch:
+class CoStreamBatch(StreamBatch):
     """B independent skeleton streams of one co-st-gcn (Model.stream_batch): every stream has its own activation
     ring, residual ring and indices for every layer, and ``step`` advances the active ones by one frame
     (stgcn_co_streams, co_streams.hip: the tap GEMM runs groups of streams against one read of the weights).  Follows
@@ -248,16 +253,12 @@ class CoStreamBatch:
     stream, as it does for the single-stream model."""
 
     def __init__(self, model, B, splits=0):
-        if int(B) != B or B < 1:
-            raise RuntimeError(f"stgcn_amd: stream_batch needs B >= 1, got {B}")
-        K.L.require_device(model.A)
+        super().__init__(model, B)
         if model.fcn_in.in_channels != 3 or model.norm_in.weight.shape[0] != 3:
             raise RuntimeError("stgcn_amd: co-st-gcn per-frame input head takes in_feat == 3")
         if len(model.gcn_networks) > K.L.RT_MAX_LAYERS:
             raise RuntimeError(f"stgcn_amd: co-st-gcn supports at most {K.L.RT_MAX_LAYERS} layers")
-        self.model, self.B, self.V, self.splits = model, int(B), model.A.shape[-1], int(splits)
-        self._all = torch.ones(self.B, dtype=torch.int32, device=model.A.device)
-        self.state, self._scratch, self._dtype, self._pack = [], None, None, None
+        self.splits, self._scratch, self._dtype = int(splits), None, None
         self._desc()
 
     # ------------------------------------------------------------------ buffers: once per (device, compute dtype)
@@ -270,7 +271,7 @@ class CoStreamBatch:
         for i, l in enumerate(m.gcn_networks):
             y = d.layers[i]
             y.Cin, y.Cout, y.P, y.Kt, y.S = l.in_channels, l.out_channels, m.A.shape[0], l.gamma, l.stride
-            y.res_mode = 2 if l.is_residual_conv else (1 if l.is_residual else 0)
+            y.res_mode = res_mode_of(l)
             y.splits = self.splits
         nbytes = []
         for i in range(d.L):
@@ -294,7 +295,6 @@ class CoStreamBatch:
         self._scratch = dict(layers=scratch, h0=torch.empty((B, V, d.C0), device=dev),
                              order=torch.zeros(B + 1, dtype=torch.int32, device=dev))
         self._dtype = (dt, dev)
-        self.state_bytes = sum(t.numel() * t.element_size() for ts in self.state for t in ts)
         self.scratch_bytes = sum(t.numel() * t.element_size() for sc in scratch for t in sc.values() if t is not None) \
             + sum(self._scratch[k].numel() * 4 for k in ("h0", "order"))
 
@@ -307,56 +307,23 @@ class CoStreamBatch:
             d, nbytes = self._shapes()
             if self._dtype != (m.compute_dtype, m.A.device):
                 self._alloc(d, nbytes)
-            V, P, dt, keep = self.V, m.A.shape[0], m.compute_dtype, []
-
-            def p(t):
-                keep.append(t)
-                return t.data_ptr()
-
-            def f32(t):
-                return t.detach().float().contiguous()
-
-            d.ln_w, d.ln_b = p(LF._flat_ln(m.norm_in.weight)), p(LF._flat_ln(m.norm_in.bias))
-            d.w_in, d.b_in = p(f32(m.fcn_in.weight).reshape(d.C0, -1)), p(f32(m.fcn_in.bias))
-            d.w_out, d.b_out = p(f32(m.fcn_out.weight).reshape(d.K, -1)), p(f32(m.fcn_out.bias))
+            P, dt = m.A.shape[0], m.compute_dtype
+            p = keep = Keep()
+            fill_heads(d, m, keep)
             d.h0, d.order = self._scratch["h0"].data_ptr(), self._scratch["order"].data_ptr()
             for i, l in enumerate(m.gcn_networks):
-                C = l.out_channels
-                A_eff = f32(m.A * m.edge_importance[i])
                 y, sc = d.layers[i], self._scratch["layers"][i]
-                y.A = p(A_eff)
+                _fill_layer(y, l, f32(m.A * m.edge_importance[i]), keep, dt)
                 y.wp = p(K.rt_streams_pack_weight(l.gcn.conv.weight, P))
-                y.bias2d = p(K.gcn_bias(A_eff, f32(l.gcn.conv.bias), 1, C))
                 if l.is_residual_conv:
-                    y.wrp, y.br = p(K.rt_streams_pack_weight(l.residual[0].weight, 1)), p(f32(l.residual[0].bias))
-                    y.lnr_w, y.lnr_b = p(LF._flat_ln(l.residual[1].weight)), p(LF._flat_ln(l.residual[1].bias))
-                    y.r_buf = sc["r"].data_ptr()
-                y.ln1_w, y.ln1_b = p(LF._flat_ln(l.tcn[0].weight)), p(LF._flat_ln(l.tcn[0].bias))
-                y.ln2_w, y.ln2_b = p(LF._flat_ln(l.tcn[3].weight)), p(LF._flat_ln(l.tcn[3].bias))
-                y.wt, y.bt = p(K.co_pack_weight(l.tcn[2].weight, dt)), p(f32(l.tcn[2].bias))
+                    y.wrp, y.r_buf = p(K.rt_streams_pack_weight(l.residual[0].weight, 1)), sc["r"].data_ptr()
                 y.ring, y.res_ring, y.idx = (t.data_ptr() for t in self.state[i])
                 y.z_buf, y.partial, y.y = sc["z"].data_ptr(), sc["partial"].data_ptr(), sc["y"].data_ptr()
             self._pack = (key, (d, keep))
             self.reset()  # the rings' empty content depends on tcn.0.bias: every stream restarts
         return self._pack[1]
 
-    def step(self, x, active=None):
-        """x (B, 3, 1, V) -> (B, num_classes, 1).  ``active``: None (every stream steps), an int32 device tensor
-        [B] of codes (0 skip: state untouched, zero output row; 1 step; 2 restart then step) used as given with no
-        host sync, or a bool tensor / Python list converted on the host (True = step)."""
-        B, V = self.B, self.V
-        if x.dim() != 4 or tuple(x.shape) != (B, 3, 1, V):
-            raise RuntimeError(f"stgcn_amd: CoStreamBatch.step expects x of shape {(B, 3, 1, V)}, got {tuple(x.shape)}")
-        K.L.require_device(x)
-        x = K._f32c(x)
-        if active is None:
-            active = self._all
-        elif not (torch.is_tensor(active) and active.dtype == torch.int32 and active.is_cuda):
-            active = torch.as_tensor(active).to(device=x.device, dtype=torch.int32)
-        if tuple(active.shape) != (B,) or not active.is_contiguous():
-            raise RuntimeError(f"stgcn_amd: CoStreamBatch.step expects active of shape ({B},)")
-        d, _keep = self._desc()
-        out = torch.empty((B, d.K, 1), dtype=torch.float32, device=x.device)
+    def _launch(self, d, x, active, out):
         with K.device_of(x):
             return K.co_streams(d, x, active, out)
 
@@ -367,7 +334,6 @@ class CoStreamBatch:
         sel = slice(None) if streams is None else torch.as_tensor(list(streams), dtype=torch.long,
                                                                     device=self.model.A.device)
         for l, (ring, res_ring, idx) in zip(self.model.gcn_networks, self.state):
-            b = torch.relu(l.tcn[0].bias.detach().float()).reshape(l.out_channels, self.V).t()
-            ring[sel] = b.to(ring.dtype)
+            ring[sel] = empty_ring_row(l, self.V).to(ring.dtype)
             res_ring[sel] = 0
             idx[sel] = 0

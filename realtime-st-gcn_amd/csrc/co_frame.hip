@@ -13,8 +13,11 @@
 //               frame's V <= 32 rows are the 32-row MFMA operand, 32x32x16 bf16 or 8 x 32x32x2 fp32 per 16 kk.
 //               Weights are packed once [tile][k-step][lane][8] (co_pack_kernel): lane l's B fragment of a k-step
 //               is 8 contiguous elements, a workgroup's k-step range one contiguous panel read exactly once.
-//   co_finish : u = bias + sum_s partial[s] (fixed order), y = relu(LN2(u) + res_ring[(rhead + Kt/2) % R]);
-//               advances both ring heads.                                                            (1 block)
+//   co_finish : co_finish_stage: u = bias + sum_s partial[s] (fixed order), y = relu(LN2(u) + res_ring[(rhead +
+//               Kt/2) % R]); advances both ring heads.                                               (1 block)
+// co_finish_stage and the shape limits are frame_ops.h's, shared with co_streams.hip (one stream here is its stream 0
+// of 1).  co_gcn, co_push and the ring fragment load of co_taps keep their own bodies: shared with rt_gcn_kernel /
+// cs_push / cs_taps they measured slower or took more registers here.
 // head' = (head + fifo - 1) % fifo is the slot of the newest frame: co_push / co_taps / co_finish all derive it
 // from the stored head, co_finish stores it.  Entry of age j lives in slot (head' + j) % fifo.
 // No floating-point atomics anywhere: a stream replays bit-identically.
@@ -26,15 +29,9 @@
 namespace {
 
 constexpr int NT = 256;
-constexpr int CB = 2;  // output channels per co_gcn block
-constexpr int VMAX = 32;
-constexpr int CMAX = 256;
-constexpr int PMAX = 3;
-constexpr int KTMAX = 69;
-constexpr int FNT = 1024;  // co_push / co_finish block
-constexpr int U4 = 2;      // float4 units per thread there: V * C <= 8192
+constexpr int FNT = 1024;  // co_push / co_finish block: V * C <= 8192 in 2 float4 units per thread
 
-// y_p[u][co] = W_p[co] . x[u] for the block's CB channels, then z[v][co] = bias2d[v][co] + sum_{p,u} A[p][u][v] y_p[u][co];
+// y_p[u][co] = W_p[co] . x[u] for the block's GCN_CB channels, then z[v][co] = bias2d[v][co] + sum_{p,u} A[p][u][v] y_p[u][co];
 // r[v][co] = br[co] + Wr[co] . x[v]
 __global__ __launch_bounds__(NT) void co_gcn_kernel(const float* __restrict__ x, int V, int Cin, int Cout, int P,
                                                     const float* __restrict__ A, const float* __restrict__ W,
@@ -43,32 +40,32 @@ __global__ __launch_bounds__(NT) void co_gcn_kernel(const float* __restrict__ x,
                                                     float* __restrict__ r_out) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   float* xs = sm;               // [V][Cin]
-  float* ys = xs + V * Cin;     // [P][V][CB]
-  float* As = ys + P * V * CB;  // [P][V][V]
+  float* ys = xs + V * Cin;     // [P][V][GCN_CB]
+  float* As = ys + P * V * GCN_CB;  // [P][V][V]
   const int tid = threadIdx.x, kk = tid & 7, K4 = Cin / 4;
   for (int i = tid; i < V * Cin / 4; i += NT) reinterpret_cast<float4*>(xs)[i] = reinterpret_cast<const float4*>(x)[i];
   for (int i = tid; i < P * V * V; i += NT) As[i] = A[i];
   __syncthreads();
-  const int co0 = blockIdx.x * CB;
-  for (int t0 = 0; t0 < P * V * CB; t0 += NT / 8) {
+  const int co0 = blockIdx.x * GCN_CB;
+  for (int t0 = 0; t0 < P * V * GCN_CB; t0 += NT / 8) {
     const int t = t0 + (tid >> 3);
-    const int cl = t % CB, pu = t / CB, u = pu % V, p = pu / V;
-    const bool ok = t < P * V * CB && co0 + cl < Cout;
+    const int cl = t % GCN_CB, pu = t / GCN_CB, u = pu % V, p = pu / V;
+    const bool ok = t < P * V * GCN_CB && co0 + cl < Cout;
     const int co = ok ? co0 + cl : co0;
     const float y = dot8(W + ((long)(ok ? p : 0) * Cout + co) * Cin, xs + (ok ? u : 0) * Cin, K4, kk);
-    if (ok && kk == 0) ys[t] = y;  // t = (p * V + u) * CB + cl
+    if (ok && kk == 0) ys[t] = y;  // t = (p * V + u) * GCN_CB + cl
   }
   __syncthreads();
-  for (int t0 = 0; t0 < V * CB; t0 += NT / 8) {
+  for (int t0 = 0; t0 < V * GCN_CB; t0 += NT / 8) {
     const int tr = t0 + (tid >> 3);
-    const int cl = tr % CB, v = tr / CB, co = co0 + cl;
+    const int cl = tr % GCN_CB, v = tr / GCN_CB, co = co0 + cl;
     const bool ok = v < V && co < Cout;
     float r = 0.f;
     if (Wr) r = dot8(Wr + (long)(ok ? co : co0) * Cin, xs + (ok ? v : 0) * Cin, K4, kk);
     if (ok && kk == 0) {
       float s = bias2d ? bias2d[v * Cout + co] : 0.f;
       for (int p = 0; p < P; ++p)
-        for (int u = 0; u < V; ++u) s = fmaf(As[(p * V + u) * V + v], ys[(p * V + u) * CB + cl], s);
+        for (int u = 0; u < V; ++u) s = fmaf(As[(p * V + u) * V + v], ys[(p * V + u) * GCN_CB + cl], s);
       const long e = (long)v * Cout + co;
       z_out[e] = s;
       if (Wr) r_out[e] = r + (br ? br[co] : 0.f);
@@ -76,31 +73,29 @@ __global__ __launch_bounds__(NT) void co_gcn_kernel(const float* __restrict__ x,
   }
 }
 
-DEV float2 ln_stats_reg(const float4 (&v)[U4], int n4, float* red) { return ln_stats_units<FNT>(v, n4, red); }
-
+// the body co_push_stage restates for co_streams.hip: kept apart, the shared stage measured 0.3 us slower here
 template <typename T>
 __global__ __launch_bounds__(FNT) void co_push_kernel(const stgcn_co_layer d) {
   __shared__ float red[FNT / 64];
   const int tid = threadIdx.x, V = d.V, C = d.Cout, n4 = V * C / 4;
-  const int fifo = d.S * (d.Kt - 1) + 1, R = d.Kt / 2 + 1;
-  const int head = (d.idx[0] + fifo - 1) % fifo, rhead = (d.idx[1] + R - 1) % R;
-  float4 z[U4], r[U4];
+  const int head = ring_head(d.idx[0], ring_slots(d.S, d.Kt)), rhead = ring_head(d.idx[1], res_slots(d.Kt));
+  float4 z[co_units(FNT)], r[co_units(FNT)];
   const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
-  for (int j = 0; j < U4; ++j) {
+  for (int j = 0; j < co_units(FNT); ++j) {
     const int e4 = tid + FNT * j;
     z[j] = e4 < n4 ? reinterpret_cast<const float4*>(d.z_buf)[e4] : zero;
     r[j] = zero;
     if (e4 < n4 && d.res_mode == 1) r[j] = reinterpret_cast<const float4*>(d.x)[e4];
     if (e4 < n4 && d.res_mode == 2) r[j] = reinterpret_cast<const float4*>(d.r_buf)[e4];
   }
-  const float2 st = ln_stats_reg(z, n4, red);
+  const float2 st = ln_stats_units<FNT>(z, n4, red);
   float2 sr = make_float2(0.f, 1.f);
-  if (d.res_mode == 2) sr = ln_stats_reg(r, n4, red);
+  if (d.res_mode == 2) sr = ln_stats_units<FNT>(r, n4, red);
   T* slot = reinterpret_cast<T*>(d.ring) + (long)head * V * C;
   float* rslot = d.res_ring + (long)rhead * V * C;
 #pragma unroll
-  for (int j = 0; j < U4; ++j) {
+  for (int j = 0; j < co_units(FNT); ++j) {
     const int e4 = tid + FNT * j;
     if (e4 < n4) {
       float4 o = ln_apply4(z[j], st, d.ln1_w, d.ln1_b, e4, V, C);
@@ -147,7 +142,7 @@ __global__ __launch_bounds__(NT) void co_taps_kernel(const T* __restrict__ wt, c
   __shared__ float red[TW][16][64];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, row = lane & 31, h = lane >> 5;
   const int tile = blockIdx.x, s = blockIdx.y;
-  const int fifo = S * (Kt - 1) + 1, head = (idx[0] + fifo - 1) % fifo, Ktot = Kt * C;
+  const int fifo = ring_slots(S, Kt), head = ring_head(idx[0], fifo), Ktot = Kt * C;
   const int ks0 = (int)((long)s * nks / nsplit), ks1 = (int)((long)(s + 1) * nks / nsplit);
   const T* panel = wt + (long)tile * nks * 512;
   f32x16 acc;
@@ -197,55 +192,13 @@ __global__ __launch_bounds__(NT) void co_pack_kernel(const float* __restrict__ w
 
 __global__ __launch_bounds__(FNT) void co_finish_kernel(const stgcn_co_layer d, int nsplit) {
   __shared__ float red[FNT / 64];
-  const int tid = threadIdx.x, V = d.V, C = d.Cout, n4 = V * C / 4;
-  const int fifo = d.S * (d.Kt - 1) + 1, R = d.Kt / 2 + 1;
-  const int head = (d.idx[0] + fifo - 1) % fifo, rhead = (d.idx[1] + R - 1) % R;
-  const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-  float4 u[U4];
-#pragma unroll
-  for (int j = 0; j < U4; ++j) {
-    const int e4 = tid + FNT * j;
-    u[j] = zero;
-    if (e4 < n4) {
-      const int c = (e4 * 4) % C;
-      float4 t = d.bt ? *reinterpret_cast<const float4*>(d.bt + c) : zero;
-      const float4* p = reinterpret_cast<const float4*>(d.partial) + e4;
-#pragma unroll 4
-      for (int s = 0; s < nsplit; ++s) {
-        const float4 q = p[(long)s * n4];
-        t.x += q.x, t.y += q.y, t.z += q.z, t.w += q.w;
-      }
-      u[j] = t;
-    }
-  }
-  const float2 st = ln_stats_reg(u, n4, red);
-  const float* rslot = d.res_ring + (long)((rhead + d.Kt / 2) % R) * V * C;
-#pragma unroll
-  for (int j = 0; j < U4; ++j) {
-    const int e4 = tid + FNT * j;
-    if (e4 < n4) {
-      float4 o = ln_apply4(u[j], st, d.ln2_w, d.ln2_b, e4, V, C);
-      if (d.res_mode) {
-        const float4 r = reinterpret_cast<const float4*>(rslot)[e4];
-        o.x += r.x, o.y += r.y, o.z += r.z, o.w += r.w;
-      }
-      o = make_float4(fmaxf(o.x, 0.f), fmaxf(o.y, 0.f), fmaxf(o.z, 0.f), fmaxf(o.w, 0.f));
-      reinterpret_cast<float4*>(d.y)[e4] = o;
-    }
-  }
-  __syncthreads();  // every read of idx precedes the update
-  if (tid == 0) {
-    d.idx[0] = head;
-    d.idx[1] = rhead;
-  }
+  co_finish_stage<FNT>(co_view(d, d.V, d.x, 0), d.partial, nsplit, red);
 }
 
 bool shape_ok(int V, int Cin, int Cout, int P, int Kt, int S) {
   return V >= 2 && V <= VMAX && Cin >= 4 && Cin <= CMAX && Cin % 4 == 0 && Cout >= 4 && Cout <= CMAX &&
          Cout % 4 == 0 && P >= 1 && P <= PMAX && Kt >= 1 && Kt <= KTMAX && (Kt & 1) && (S == 1 || S == 2);
 }
-
-int num_ksteps(int C, int Kt) { return (Kt * C + 15) / 16; }
 
 }  // namespace
 
@@ -320,9 +273,9 @@ int co_pack_rows_launch(const float* w, int groups, int rows, int C, void* dst, 
 }
 
 int co_gcn_launch(const stgcn_co_layer& d, hipStream_t s) {
-  const size_t lds = ((size_t)d.V * d.Cin + (size_t)d.P * d.V * CB + (size_t)d.P * d.V * d.V) * sizeof(float);
-  hipLaunchKernelGGL(co_gcn_kernel, dim3((unsigned)((d.Cout + CB - 1) / CB)), dim3(NT), lds, s, d.x, d.V, d.Cin, d.Cout,
-                     d.P, d.A, d.w, d.bias2d, d.res_mode == 2 ? d.wr : nullptr, d.br, d.z_buf, d.r_buf);
+  const size_t lds = ((size_t)d.V * d.Cin + (size_t)d.P * d.V * GCN_CB + (size_t)d.P * d.V * d.V) * sizeof(float);
+  hipLaunchKernelGGL(co_gcn_kernel, dim3((unsigned)((d.Cout + GCN_CB - 1) / GCN_CB)), dim3(NT), lds, s, d.x, d.V, d.Cin,
+                     d.Cout, d.P, d.A, d.w, d.bias2d, d.res_mode == 2 ? d.wr : nullptr, d.br, d.z_buf, d.r_buf);
   return hipGetLastError() == hipSuccess ? STGCN_OK : STGCN_EHIP;
 }
 

@@ -4,20 +4,21 @@
 // then step, anything else step).  One tick = these launches on one stream, every hand-off a kernel boundary:
 //
 //   cs_order  : order[0] = number of active streams, order[1..] = their slots (the tap stage's groups)       (1 block)
-//   cs_in     : h0[b] = fcn_in(LayerNorm([3,1,V])(x[b]))                                          (1 block per stream)
+//   cs_in     : h0[b] = fcn_in(LayerNorm([3,1,V])(x[b])): frame_head_in                           (1 block per stream)
 //   per layer:
 //   cs_gcn    : z[b] = gcn(x[b], A), r[b] = Wr x[b] + br.  One block per stream, x[b] in LDS; a wave owns a 32-channel
 //               tile: per partition p, Y_p = x W_p^T on v_mfma_f32_32x32x2_f32 with the packed weight image (the B
-//               operand), then the A-mix on the accumulators where they are (rt_streams.hip's step (1)), summed over p
-//               in the same accumulator: z never passes through LDS.
-//   cs_push   : co_push per stream.  Code 2 first makes every other ring slot ReLU(ln1_b), every other residual slot
-//               zero and takes idx as (0, 0).
+//               operand: conv_tile_acc), then the A-mix on the accumulators where they are (amix_coeffs / amix_mma),
+//               summed over p in the same accumulator: z never passes through LDS.
+//   cs_push   : co_push_stage per stream.  Code 2 first makes every other ring slot ReLU(ln1_b), every other residual
+//               slot zero and takes idx as (0, 0).
 //   cs_taps   : the tap GEMM.  Grid (K splits) x (groups of G = 4 active streams); the 8 waves of a block share out the
 //               layer's column tiles (taps_nsub), so one block covers every column tile of its (split, group): a weight
 //               B fragment is loaded once and meets the G streams' A fragments (G MFMAs), and the column tiles'
 //               re-reads of a ring element come from the same CU: HBM sees the element once.
-//   cs_finish : co_finish per stream.
-//   cs_out    : out[b] = fcn_out(mean_v y_last[b]); zeros for a skipped stream.
+//   cs_finish : co_finish_stage per stream.
+//   cs_out    : out[b] = fcn_out(mean_v y_last[b]): frame_head_out; zeros for a skipped stream.
+// The stages, the ring fragment loads (ring_unit / load_ring) and the shape limits are frame_ops.h's.
 //
 // Order of every sum: k-steps in sequence within a wave, the nsub K-interleaves of a tile in index order, the splits
 // in index order, LayerNorm statistics as in co_frame.hip.  nsub and the default split count are functions of the
@@ -33,11 +34,7 @@ namespace {
 constexpr int HNT = 256;   // cs_order / cs_in / cs_out block
 constexpr int GNT = 512;   // cs_gcn block
 constexpr int GNW = GNT / 64;
-constexpr int XPAD = 4;    // xs row stride = Cin + XPAD floats: a fragment read's 32 rows spread over the banks
-constexpr int VMAX = 32;
-constexpr int CMAX = 256;
-constexpr int FNT = 1024;  // cs_push / cs_finish block
-constexpr int U4 = 2;      // float4 units per thread there: V * C <= 8192
+constexpr int FNT = 1024;  // cs_push / cs_finish block: V * C <= 8192 in 2 float4 units per thread
 constexpr int TNT = 512;   // cs_taps block
 constexpr int TNW = TNT / 64;
 constexpr int G = 4;       // streams per tap block: 4 x 16 accumulator registers per wave
@@ -45,8 +42,6 @@ constexpr int GTU = 4;     // k-steps in flight per wave in cs_gcn
 constexpr int MAX_SPLITS = 8;
 
 using layer_t = stgcn_co_streams_layer;
-
-DEV int fifo_of(const layer_t& y) { return y.S * (y.Kt - 1) + 1; }
 
 // ---------------------------------------------------------------------------------------------------- heads
 __global__ __launch_bounds__(HNT) void cs_order_kernel(const int* __restrict__ active, int B, int* __restrict__ order) {
@@ -64,65 +59,30 @@ __global__ __launch_bounds__(HNT) void cs_order_kernel(const int* __restrict__ a
   if (tid == HNT - 1) order[0] = at;
 }
 
-// LayerNorm([3,1,V]) + fcn_in of one stream's frame (rt_in_kernel's arithmetic) -> h0[b] rows [V][C0]
+// frame_head_in of one stream's frame -> h0[b] rows [V][C0]
 __global__ __launch_bounds__(HNT) void cs_in_kernel(const float* __restrict__ x, const int* __restrict__ active, int V,
                                                     int C0, const float* __restrict__ ln_w,
                                                     const float* __restrict__ ln_b, const float* __restrict__ w_in,
                                                     const float* __restrict__ b_in, float* __restrict__ h0) {
   __shared__ float xi[3 * VMAX];
   __shared__ float red[HNT / 64];
-  const int tid = threadIdx.x, n = 3 * V;
   const long b = blockIdx.x;
   if (active[b] == 0) return;
-  for (int i = tid; i < n; i += HNT) xi[i] = x[b * n + i];
-  __syncthreads();
-  float s = 0.f;
-  for (int i = tid; i < n; i += HNT) s += xi[i];
-  const float mean = block_sum(s, red) / (float)n;
-  float q = 0.f;
-  for (int i = tid; i < n; i += HNT) {
-    const float t = xi[i] - mean;
-    q = fmaf(t, t, q);
-  }
-  const float rstd = 1.f / sqrtf(block_sum(q, red) / (float)(n - 1) + 1e-5f);
-  __syncthreads();
-  for (int i = tid; i < n; i += HNT) xi[i] = fmaf(ln_w[i], (xi[i] - mean) * rstd, ln_b[i]);
-  __syncthreads();
-  float* out = h0 + b * V * C0;
-  for (int i = tid; i < V * C0; i += HNT) {
-    const int v = i / C0, co = i - v * C0;
-    float t = b_in[co];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) t = fmaf(w_in[co * 3 + c], xi[c * V + v], t);
-    out[i] = t;
-  }
+  frame_head_in<HNT>(x + b * 3 * V, V, C0, ln_w, ln_b, w_in, b_in, xi, red, h0 + b * V * C0, C0);
 }
 
-// pool over the joints + fcn_out (rt_out_kernel's arithmetic); a zero row for a skipped stream
+// frame_head_out of one stream's last rows; a zero row for a skipped stream
 __global__ __launch_bounds__(HNT) void cs_out_kernel(const float* __restrict__ y, const int* __restrict__ active, int V,
                                                      int C, const float* __restrict__ w_out,
                                                      const float* __restrict__ b_out, int K, float* __restrict__ out) {
   __shared__ float pool[CMAX];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const long b = blockIdx.x;
   float* o = out + b * K;
   if (active[b] == 0) {
-    for (int k = tid; k < K; k += HNT) o[k] = 0.f;
+    for (int k = threadIdx.x; k < K; k += HNT) o[k] = 0.f;
     return;
   }
-  const float* yb = y + b * V * C;
-  for (int c = tid; c < C; c += HNT) {
-    float s = 0.f;
-    for (int v = 0; v < V; ++v) s += yb[v * C + c];
-    pool[c] = s / (float)V;
-  }
-  __syncthreads();
-  for (int k = w; k < K; k += HNT / 64) {  // one wave per class, the channels over the lanes
-    float s = 0.f;
-    for (int c = lane; c < C; c += 64) s = fmaf(w_out[(long)k * C + c], pool[c], s);
-    s = wave_sum(s);
-    if (lane == 0) o[k] = s + (b_out ? b_out[k] : 0.f);
-  }
+  frame_head_out<HNT>(y + b * V * C, C, V, C, w_out, b_out, K, pool, o);
 }
 
 // ---------------------------------------------------------------------------------------------------- gcn
@@ -150,27 +110,13 @@ __global__ __launch_bounds__(GNT) void cs_gcn_kernel(const layer_t ly, int V, co
     for (int r = 0; r < 16; ++r) z[r] = 0.f;
     for (int p = 0; p < (res ? 1 : P); ++p) {
       const float* panel = (res ? ly.wrp : ly.wp + (long)p * ntile * nks * 512) + (long)tile * nks * 512;
-      f32x16 acc;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-      for (int kb = 0; kb < nks; kb += GTU) {
-        f32x8 fa[GTU], fb[GTU];
-#pragma unroll
-        for (int u = 0; u < GTU; ++u) fb[u] = load_b<float>(panel, kb + u, nks, lane);
-#pragma unroll
-        for (int u = 0; u < GTU; ++u) fa[u] = load_a(xs, ldx, kb + u, nks, row, h, V, Cin);
-#pragma unroll
-        for (int u = 0; u < GTU; ++u) Tr<float>::mma(acc, fa[u], fb[u]);
-      }
+      const f32x16 acc = conv_tile_acc<float, GTU>(panel, xs, ldx, nks, row, h, V, Cin, lane);
       if (res) {
         z = acc;
-      } else {  // z[v][co] += sum_u A_p[u][v] Y_p[u][co]: accumulator register r is the B operand of k = acc_row(r, .)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int u = acc_row(r, lane);
-          const float am = (u < V && row < V) ? ly.A[(p * V + u) * V + row] : 0.f;
-          z = __builtin_amdgcn_mfma_f32_32x32x2f32(am, acc[r], z, 0, 0, 0);
-        }
+      } else {  // z[v][co] += sum_u A_p[u][v] Y_p[u][co]
+        float am[16];
+        amix_coeffs(ly.A, p, V, lane, true, am);
+        amix_mma(am, acc, z);
       }
     }
     const int co = tile * 32 + row;
@@ -187,8 +133,6 @@ __global__ __launch_bounds__(GNT) void cs_gcn_kernel(const layer_t ly, int V, co
 }
 
 // ---------------------------------------------------------------------------------------------------- push
-DEV float2 ln_stats_reg(const float4 (&v)[U4], int n4, float* red) { return ln_stats_units<FNT>(v, n4, red); }
-
 template <typename T>
 __global__ __launch_bounds__(FNT) void cs_push_kernel(const layer_t ly, int V, const float* __restrict__ x,
                                                       const int* __restrict__ active) {
@@ -198,49 +142,25 @@ __global__ __launch_bounds__(FNT) void cs_push_kernel(const layer_t ly, int V, c
   const int code = active[b];
   if (code == 0) return;
   const bool restart = code == 2;
-  const int fifo = fifo_of(ly), R = ly.Kt / 2 + 1;
-  const int i0 = restart ? 0 : ly.idx[b * 2], i1 = restart ? 0 : ly.idx[b * 2 + 1];
-  const int head = (i0 + fifo - 1) % fifo, rhead = (i1 + R - 1) % R;
+  const int fifo = ring_slots(ly.S, ly.Kt), R = res_slots(ly.Kt);
+  const int head = ring_head(restart ? 0 : ly.idx[b * 2], fifo), rhead = ring_head(restart ? 0 : ly.idx[b * 2 + 1], R);
+  const CoView d = co_view(ly, V, x, b);
   T* ring = reinterpret_cast<T*>(ly.ring) + b * fifo * E;
-  float* res_ring = ly.res_ring + b * R * E;
-  const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
   if (restart) {  // an empty FIFO: ReLU(LN1(0)) = ReLU(ln1_b) in every slot but the one written below; residuals zero
 #pragma unroll
-    for (int j = 0; j < U4; ++j) {
+    for (int j = 0; j < co_units(FNT); ++j) {
       const int e4 = tid + FNT * j;
       if (e4 < n4) {
         const float4 f = relu4(ln_param4(ly.ln1_b, e4, V, C));
         for (int s = 0; s < fifo; ++s)
           if (s != head) store4(ring + s * E + e4 * 4, f);
         for (int s = 0; s < R; ++s)
-          if (s != rhead) store4(res_ring + s * E + e4 * 4, zero);
+          if (s != rhead) store4(d.res_ring + s * E + e4 * 4, make_float4(0.f, 0.f, 0.f, 0.f));
       }
     }
     if (tid == 0) ly.idx[b * 2] = 0, ly.idx[b * 2 + 1] = 0;  // what cs_taps and cs_finish read; nobody else reads them here
   }
-  float4 z[U4], r[U4];
-#pragma unroll
-  for (int j = 0; j < U4; ++j) {
-    const int e4 = tid + FNT * j;
-    z[j] = e4 < n4 ? reinterpret_cast<const float4*>(ly.z_buf + b * E)[e4] : zero;
-    r[j] = zero;
-    if (e4 < n4 && ly.res_mode == 1) r[j] = reinterpret_cast<const float4*>(x + b * E)[e4];  // Cin == Cout
-    if (e4 < n4 && ly.res_mode == 2) r[j] = reinterpret_cast<const float4*>(ly.r_buf + b * E)[e4];
-  }
-  const float2 st = ln_stats_reg(z, n4, red);
-  float2 sr = make_float2(0.f, 1.f);
-  if (ly.res_mode == 2) sr = ln_stats_reg(r, n4, red);
-  T* slot = ring + head * E;
-  float* rslot = res_ring + rhead * E;
-#pragma unroll
-  for (int j = 0; j < U4; ++j) {
-    const int e4 = tid + FNT * j;
-    if (e4 < n4) {
-      store4(slot + e4 * 4, relu4(ln_apply4(z[j], st, ly.ln1_w, ly.ln1_b, e4, V, C)));
-      if (ly.res_mode == 1) store4(rslot + e4 * 4, r[j]);
-      if (ly.res_mode == 2) store4(rslot + e4 * 4, ln_apply4(r[j], sr, ly.lnr_w, ly.lnr_b, e4, V, C));
-    }
-  }
+  co_push_stage<T, FNT>(d, ring, head, rhead, red);
 }
 
 // ---------------------------------------------------------------------------------------------------- taps
@@ -248,28 +168,6 @@ __global__ __launch_bounds__(FNT) void cs_push_kernel(const layer_t ly, int V, c
 // k-steps (wave (tile, sub) takes ks0 + sub, ks0 + sub + nsub, ...); with more than 8 tiles a wave would loop, but
 // Cout <= 256 gives at most 8.  A function of Cout alone.
 DEV int taps_nsub(int ntile) { return ntile >= TNW ? 1 : TNW / ntile; }
-
-// A fragment of one stream: 8 consecutive kk = tap * C + ci from slot (head + tap * S) % fifo, row `row`
-template <typename T>
-DEV typename Tr<T>::frag load_ring(const T* __restrict__ ring, bool ok, int row, int V, int C, int S, int fifo, int head,
-                                   const int (&tap)[2], const int (&ci)[2], const bool (&in)[2]) {
-  T f[8];
-#pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    if (ok && in[u]) {
-      int slot = head + tap[u] * S;  // head < fifo, tap * S <= fifo - 1
-      if (slot >= fifo) slot -= fifo;
-      load4(ring + ((long)slot * V + row) * C + ci[u], f + 4 * u);
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) f[4 * u + i] = (T)0.f;
-    }
-  }
-  typename Tr<T>::frag a;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) a[j] = f[j];
-  return a;
-}
 
 template <typename T, int TU>
 __global__ __launch_bounds__(TNT) void cs_taps_kernel(const layer_t ly, int V, int nks, int nsplit,
@@ -279,7 +177,7 @@ __global__ __launch_bounds__(TNT) void cs_taps_kernel(const layer_t ly, int V, i
   if (g0 >= nact) return;  // uniform over the block
   const int ng = min(G, nact - g0);
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, row = lane & 31, h = lane >> 5;
-  const int C = ly.Cout, Kt = ly.Kt, S = ly.S, fifo = fifo_of(ly), Ktot = Kt * C;
+  const int C = ly.Cout, Kt = ly.Kt, S = ly.S, fifo = ring_slots(S, Kt), Ktot = Kt * C;
   const int ntile = (C + 31) / 32, nsub = taps_nsub(ntile);
   const int tile = w / nsub, sub = w - tile * nsub;
   const bool work = tile < ntile;  // uniform over the wave
@@ -291,7 +189,7 @@ __global__ __launch_bounds__(TNT) void cs_taps_kernel(const layer_t ly, int V, i
 #pragma unroll
   for (int g = 0; g < G; ++g) {
     sb[g] = g < ng ? order[1 + g0 + g] : 0;
-    head[g] = g < ng ? (ly.idx[sb[g] * 2] + fifo - 1) % fifo : 0;
+    head[g] = g < ng ? ring_head(ly.idx[sb[g] * 2], fifo) : 0;
     ring[g] = reinterpret_cast<const T*>(ly.ring) + (long)sb[g] * fifo * E;
   }
   f32x16 acc[G];
@@ -307,16 +205,10 @@ __global__ __launch_bounds__(TNT) void cs_taps_kernel(const layer_t ly, int V, i
       for (int u = 0; u < TU; ++u) bf[u] = load_b<T>(panel, kb + u * nsub, ks1, lane);
 #pragma unroll
       for (int u = 0; u < TU; ++u) {
-        const int ks = kb + u * nsub;
         int tap[2], ci[2];
         bool in[2];
 #pragma unroll
-        for (int q = 0; q < 2; ++q) {
-          const int kk = ks * 16 + 8 * h + 4 * q;
-          in[q] = ks < ks1 && kk < Ktot;
-          tap[q] = in[q] ? kk / C : 0;
-          ci[q] = in[q] ? kk - tap[q] * C : 0;
-        }
+        for (int q = 0; q < 2; ++q) in[q] = ring_unit(kb + u * nsub, ks1, h, q, C, Ktot, tap[q], ci[q]);
 #pragma unroll
         for (int g = 0; g < G; ++g)
           af[u][g] = load_ring<T>(ring[g], g < ng && row < V, row, V, C, S, fifo, head[g], tap, ci, in);
@@ -352,46 +244,10 @@ __global__ __launch_bounds__(TNT) void cs_taps_kernel(const layer_t ly, int V, i
 __global__ __launch_bounds__(FNT) void cs_finish_kernel(const layer_t ly, int V, int nsplit,
                                                         const int* __restrict__ active) {
   __shared__ float red[FNT / 64];
-  const int tid = threadIdx.x, C = ly.Cout, n4 = V * C / 4;
-  const long b = blockIdx.x, E = (long)V * C;
+  const long b = blockIdx.x;
   if (active[b] == 0) return;
-  const int fifo = fifo_of(ly), R = ly.Kt / 2 + 1;
-  const int head = (ly.idx[b * 2] + fifo - 1) % fifo, rhead = (ly.idx[b * 2 + 1] + R - 1) % R;
-  const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-  float4 u[U4];
-#pragma unroll
-  for (int j = 0; j < U4; ++j) {
-    const int e4 = tid + FNT * j;
-    u[j] = zero;
-    if (e4 < n4) {
-      const int c = (e4 * 4) % C;
-      float4 t = ly.bt ? *reinterpret_cast<const float4*>(ly.bt + c) : zero;
-      const float4* p = reinterpret_cast<const float4*>(ly.partial + b * nsplit * E) + e4;
-#pragma unroll 4
-      for (int s = 0; s < nsplit; ++s) t = add4(t, p[(long)s * n4]);
-      u[j] = t;
-    }
-  }
-  const float2 st = ln_stats_reg(u, n4, red);
-  const float* rslot = ly.res_ring + (b * R + (rhead + ly.Kt / 2) % R) * E;
-  float* y = ly.y + b * E;
-#pragma unroll
-  for (int j = 0; j < U4; ++j) {
-    const int e4 = tid + FNT * j;
-    if (e4 < n4) {
-      float4 o = ln_apply4(u[j], st, ly.ln2_w, ly.ln2_b, e4, V, C);
-      if (ly.res_mode) o = add4(o, reinterpret_cast<const float4*>(rslot)[e4]);
-      reinterpret_cast<float4*>(y)[e4] = relu4(o);
-    }
-  }
-  __syncthreads();  // every read of idx precedes the update
-  if (tid == 0) {
-    ly.idx[b * 2] = head;
-    ly.idx[b * 2 + 1] = rhead;
-  }
+  co_finish_stage<FNT>(co_view(ly, V, nullptr, b), ly.partial + b * nsplit * V * ly.Cout, nsplit, red);
 }
-
-int num_ksteps(int C, int Kt) { return (Kt * C + 15) / 16; }
 
 // the single-stream descriptor that carries the same shape: co_check's limits are this route's limits
 stgcn_co_layer as_co_layer(const stgcn_co_streams_desc& d, const layer_t& y) {

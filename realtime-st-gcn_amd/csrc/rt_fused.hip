@@ -4,7 +4,7 @@
 // ~1 ms per frame, most of it tile-GEMM kernels sized for batches running a 25-row GEMM).
 //
 //   rt_in     : x (1,3,1,V) -> LayerNorm([3,1,V]) (per frame, unbiased var; layernorm.py:22-28) -> fcn_in
-//               (1x1 conv + bias; rtstgcn.py:103) -> rows [V][C0]                               (1 block)
+//               (1x1 conv + bias; rtstgcn.py:103) -> rows [V][C0]: frame_head_in                  (1 block)
 //   rt_gcn    : z = conv1x1(x) (+bias) mixed by A (tgcn as the online layer applies it, rtstgcn.py:531-537)
 //               evaluated as z[v][co] = bias2d[v][co] + sum_{p,ci} W[p*Cout+co][ci] * XA_p[v][ci],
 //               XA_p[v][ci] = sum_u A[p][u][v] x[u][ci] (A = graph * importance, OnlineLayer.eval_);
@@ -14,7 +14,8 @@
 //   rt_norm   : y = relu(relu(LN(a)) + res) (residual; res = LN_r(r) | x) or relu(LN(a)) (rtstgcn.py:538-553),
 //               LN over the frame's C*V values (two-pass mean / unbiased variance, fixed-order sums);
 //               advances the FIFO indices.                                                    (1 block)
-//   rt_out    : AvgPool over the V joints (rtstgcn.py:149) -> fcn_out (+ bias) -> (classes)      (1 block)
+//   rt_out    : AvgPool over the V joints (rtstgcn.py:149) -> fcn_out (+ bias) -> (classes): frame_head_out (1 block)
+// The stages named above are frame_ops.h's, shared with the other per-frame routes.
 // Rows are channels-last [V][C] fp32 (the layout of the rest of the package); FIFO state [fifo][V][C],
 // accumulators [S][V][C], indices int[2] (fifo, acc) — device buffers, so a HIP graph can replay frames.
 #include "common.h"
@@ -25,12 +26,8 @@
 namespace {
 
 constexpr int NT = 256;
-constexpr int CB = 2;        // output channels per rt_gcn block (Cout / 2 blocks: the weight rows stream in parallel)
-constexpr int VMAX = 32;
-constexpr int CMAX = 256;
-constexpr int PMAX = 3;
 
-// LayerNorm statistics (mean, 1/sqrt(unbiased var + eps)) of n values (two passes over the data)
+// LayerNorm statistics (mean, 1/sqrt(unbiased var + eps)) of n values (two passes over the data): rt_frame_kernel's
 DEV float2 ln_stats(const float* x, int n, float eps, float* red) {
   float s = 0.f;
   for (int i = threadIdx.x; i < n; i += blockDim.x) s += x[i];
@@ -46,28 +43,14 @@ DEV float2 ln_stats(const float* x, int n, float eps, float* red) {
 
 __global__ __launch_bounds__(NT) void rt_in_kernel(const float* __restrict__ x, int V, const float* __restrict__ g,
                                                    const float* __restrict__ b, const float* __restrict__ W,
-                                                   const float* __restrict__ bias, int C0, float eps,
-                                                   float* __restrict__ out) {
+                                                   const float* __restrict__ bias, int C0, float* __restrict__ out) {
   __shared__ float xs[3 * VMAX];
   __shared__ float red[NT / 64];
-  const int n = 3 * V;  // (3, 1, V) per frame, element c*V + v
-  for (int i = threadIdx.x; i < n; i += NT) xs[i] = x[i];
-  __syncthreads();
-  const float2 st = ln_stats(xs, n, eps, red);
-  __syncthreads();
-  for (int i = threadIdx.x; i < n; i += NT) xs[i] = fmaf(g[i], (xs[i] - st.x) * st.y, b[i]);
-  __syncthreads();
-  for (int i = threadIdx.x; i < V * C0; i += NT) {
-    const int v = i / C0, co = i - v * C0;
-    float s = bias[co];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) s = fmaf(W[co * 3 + c], xs[c * V + v], s);
-    out[i] = s;
-  }
+  frame_head_in<NT>(x, V, C0, g, b, W, bias, xs, red, out, C0);
 }
 
-// conv first, as the reference (tgcn: conv1x1 then @A): y_p[u][co] = W_p[co] . x[u] for the block's CB
-// channels (P*V*CB dot products), then z[v][co] = bias2d[v][co] + sum_{p,u} A[p][u][v] y_p[u][co]
+// conv first, as the reference (tgcn: conv1x1 then @A): y_p[u][co] = W_p[co] . x[u] for the block's GCN_CB
+// channels (P*V*GCN_CB dot products), then z[v][co] = bias2d[v][co] + sum_{p,u} A[p][u][v] y_p[u][co]
 __global__ __launch_bounds__(NT) void rt_gcn_kernel(const float* __restrict__ x, int V, int Cin, int Cout, int P,
                                                     const float* __restrict__ A, const float* __restrict__ W,
                                                     const float* __restrict__ bias2d, float* fifo, float* acc,
@@ -75,34 +58,34 @@ __global__ __launch_bounds__(NT) void rt_gcn_kernel(const float* __restrict__ x,
                                                     float* __restrict__ a_out, float* __restrict__ r_out) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   float* xs = sm;                 // [V][Cin]
-  float* ys = xs + V * Cin;       // [P][V][CB]
-  float* As = ys + P * V * CB;    // [P][V][V]
+  float* ys = xs + V * Cin;       // [P][V][GCN_CB]
+  float* As = ys + P * V * GCN_CB;    // [P][V][V]
   const int tid = threadIdx.x, kk = tid & 7, K4 = Cin / 4;
   for (int i = tid; i < V * Cin / 4; i += NT) reinterpret_cast<float4*>(xs)[i] = reinterpret_cast<const float4*>(x)[i];
   for (int i = tid; i < P * V * V; i += NT) As[i] = A[i];
   __syncthreads();
-  const int co0 = blockIdx.x * CB;
-  for (int t0 = 0; t0 < P * V * CB; t0 += NT / 8) {
+  const int co0 = blockIdx.x * GCN_CB;
+  for (int t0 = 0; t0 < P * V * GCN_CB; t0 += NT / 8) {
     const int t = t0 + (tid >> 3);
-    const int cl = t % CB, pu = t / CB, u = pu % V, p = pu / V;
-    const bool ok = t < P * V * CB && co0 + cl < Cout;
+    const int cl = t % GCN_CB, pu = t / GCN_CB, u = pu % V, p = pu / V;
+    const bool ok = t < P * V * GCN_CB && co0 + cl < Cout;
     const int co = ok ? co0 + cl : co0;
     const float y = dot8(W + ((long)(ok ? p : 0) * Cout + co) * Cin, xs + (ok ? u : 0) * Cin, K4, kk);
-    if (ok && kk == 0) ys[t] = y;  // t = (p * V + u) * CB + cl
+    if (ok && kk == 0) ys[t] = y;  // t = (p * V + u) * GCN_CB + cl
   }
   __syncthreads();
   const int fi = idx[0], ai = idx[1];
   const long E = (long)V * Cout;
-  for (int t0 = 0; t0 < V * CB; t0 += NT / 8) {  // (v, cl) outputs, 8 lanes each
+  for (int t0 = 0; t0 < V * GCN_CB; t0 += NT / 8) {  // (v, cl) outputs, 8 lanes each
     const int tr = t0 + (tid >> 3);
-    const int cl = tr % CB, v = tr / CB, co = co0 + cl;
+    const int cl = tr % GCN_CB, v = tr / GCN_CB, co = co0 + cl;
     const bool ok = v < V && co < Cout;
     float r = 0.f;
     if (Wr) r = dot8(Wr + (long)(ok ? co : co0) * Cin, xs + (ok ? v : 0) * Cin, K4, kk);  // residual (no bias)
     if (ok && kk == 0) {
       float s = bias2d ? bias2d[v * Cout + co] : 0.f;
       for (int p = 0; p < P; ++p)
-        for (int u = 0; u < V; ++u) s = fmaf(As[(p * V + u) * V + v], ys[(p * V + u) * CB + cl], s);
+        for (int u = 0; u < V; ++u) s = fmaf(As[(p * V + u) * V + v], ys[(p * V + u) * GCN_CB + cl], s);
       const long e = (long)v * Cout + co;
       const float a = acc[ai * E + e] + s - fifo[fi * E + e];
       acc[ai * E + e] = a;
@@ -169,19 +152,7 @@ __global__ __launch_bounds__(1024) void rt_out_kernel(const float* __restrict__ 
                                                       const float* __restrict__ W, const float* __restrict__ bias,
                                                       int K, float* __restrict__ out) {
   __shared__ float pool[CMAX];
-  for (int c = threadIdx.x; c < C; c += blockDim.x) {
-    float s = 0.f;
-    for (int v = 0; v < V; ++v) s += x[v * C + c];
-    pool[c] = s / (float)V;
-  }
-  __syncthreads();
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  for (int k = w; k < K; k += nw) {  // one wave per class, the channels over the lanes
-    float s = 0.f;
-    for (int c = lane; c < C; c += 64) s = fmaf(W[(long)k * C + c], pool[c], s);
-    s = wave_sum(s);
-    if (lane == 0) out[k] = s + (bias ? bias[k] : 0.f);
-  }
+  frame_head_out<1024>(x, C, V, C, W, bias, K, pool, out);
 }
 
 // ------------------------------------------------------------------ the whole frame in one launch
@@ -679,7 +650,7 @@ extern "C" int stgcn_rt_prof(void* dst, long n) {
 int rt_in_launch(const float* x, int V, const float* g, const float* b, const float* W, const float* bias, int C0,
                  float* out, hipStream_t s) {
   if (!x || !g || !b || !W || !bias || !out || V < 2 || V > VMAX || C0 < 1) return STGCN_EBADSHAPE;
-  hipLaunchKernelGGL(rt_in_kernel, dim3(1), dim3(NT), 0, s, x, V, g, b, W, bias, C0, 1e-5f, out);
+  hipLaunchKernelGGL(rt_in_kernel, dim3(1), dim3(NT), 0, s, x, V, g, b, W, bias, C0, out);
   return hipGetLastError() == hipSuccess ? STGCN_OK : STGCN_EHIP;
 }
 
@@ -688,10 +659,10 @@ int rt_gcn_launch(const float* x, int V, int Cin, int Cout, int P, const float* 
                   hipStream_t s) {
   if (!x || !A || !W || !fifo || !acc || !idx || !a_out || (Wr && !r_out)) return STGCN_EBADSHAPE;
   if (V < 1 || V > VMAX || Cin < 4 || Cin > CMAX || Cin % 4 || Cout < 1 || P < 1 || P > PMAX) return STGCN_EBADSHAPE;
-  const size_t lds = ((size_t)V * Cin + (size_t)P * V * CB + (size_t)P * V * V) * sizeof(float);
+  const size_t lds = ((size_t)V * Cin + (size_t)P * V * GCN_CB + (size_t)P * V * V) * sizeof(float);
   if (lds > 160 * 1024) return STGCN_EBADSHAPE;
   if (stgcn_lds_attr((const void*)rt_gcn_kernel, 160 * 1024, s)) return STGCN_EHIP;
-  hipLaunchKernelGGL(rt_gcn_kernel, dim3((unsigned)((Cout + CB - 1) / CB)), dim3(NT), lds, s, x, V, Cin, Cout, P, A, W,
+  hipLaunchKernelGGL(rt_gcn_kernel, dim3((unsigned)((Cout + GCN_CB - 1) / GCN_CB)), dim3(NT), lds, s, x, V, Cin, Cout, P, A, W,
                      bias2d, fifo, acc, idx, Wr, a_out, r_out);
   return hipGetLastError() == hipSuccess ? STGCN_OK : STGCN_EHIP;
 }

@@ -1,8 +1,10 @@
 // RT-ST-GCN per-frame inference for a batch of B independent skeleton streams (stgcn_rt_streams), LayerNorm online
-// layers, conv operands fp32 or bf16 (template parameter T; all that follows the conv accumulators is fp32 in both): one workgroup per stream runs the whole network for its stream's frame (rt_fused.hip's arithmetic:
-// rt_in / rt_gcn / rt_norm / rt_out) with the layer input and output in LDS, the weights streamed from L2 (shared
-// by every workgroup) and the stream's FIFO state updated in place.  No workgroup waits on another: no grid barrier,
-// no spin, no atomics.  B may exceed the CU count; the workgroups queue.
+// layers, conv operands fp32 or bf16 (template parameter T; all that follows the conv accumulators is fp32 in both):
+// one workgroup per stream runs the whole network for its stream's frame (frame_ops.h's stages: frame_head_in, per
+// layer conv_tile_acc + amix_coeffs / amix_mma and the FIFO step + norms below, frame_head_out) with the layer input
+// and output in LDS, the weights streamed from L2 (shared by every workgroup) and the stream's FIFO state updated in
+// place.  No workgroup waits on another: no grid barrier, no spin, no atomics.  B may exceed the CU count; the
+// workgroups queue.
 //
 // Per layer (V <= 32 joint rows, zero-padded to the 32-row MFMA operand by the fragment loads):
 //   (1) tasks over the 8 waves: (partition p, 32-channel tile) of the conv, and (tile) of the residual conv.
@@ -11,12 +13,10 @@
 //       [tile][k-step][lane][8]: one contiguous piece per lane per 16-k step, read once).  LDS keeps the rows in fp32
 //       only; the bf16 A fragment is rounded (nearest even) from them as it is loaded, so the identity residual and
 //       every later step read the unrounded values.
-//       The A-mix runs on the accumulators where they are: accumulator register r of lane l holds Y_p[acc_row(r, l)][co],
-//       which IS the B operand (k = l >> 5, n = l & 31) of an MFMA whose two k are u = acc_row(r, 0) and acc_row(r, 32);
-//       with A operand A_p[u][v] (m = v) sixteen MFMAs give Z_p[v][co] = sum_u A_p[u][v] Y_p[u][co].
+//       The A-mix runs on the accumulators where they are (amix_mma): Z_p[v][co] = sum_u A_p[u][v] Y_p[u][co].
 //       Z_p -> LDS zs[p], the residual conv -> LDS rs.
 //   (2) z = bias2d + Z_0 + Z_1 + Z_2; a = acc[ai] + z - fifo[fi]; acc[ai] = a; fifo[fi] = z (rtstgcn.py:591-627);
-//       y = relu(relu(LN(a)) + res) (rt_norm_kernel's math; two-pass statistics, fixed-order sums) -> LDS xs.
+//       y = relu(relu(LN(a)) + res) (rt_fused.hip's rt_norm math; two-pass statistics ln_stats_units, fixed-order sums) -> LDS xs.
 // Every sum has a fixed order that depends on the network only: a stream's frames are bit-identical whatever B, its
 // slot and the other streams' masks are.
 #include "common.h"
@@ -28,18 +28,11 @@ namespace {
 
 constexpr int NT = 512;
 constexpr int NW = NT / 64;
-constexpr int VMAX = 32;
-constexpr int CMAX = 256;
-constexpr int PMAX = 3;
-constexpr int MAXE = 7680;                    // V * C limit (stgcn_rt_frame's)
-constexpr int XPAD = 4;                       // xs row stride = C + XPAD floats: the 32 rows of a fragment read spread over the banks
 constexpr int U4 = (MAXE / 4 + NT - 1) / NT;  // float4 units of a frame per thread
 constexpr int TU = 4;                         // k-steps in flight per wave
 constexpr int XS_FLOATS = MAXE + VMAX * XPAD;
 // dynamic LDS (floats): xs | rs | zs[PMAX] | red
 constexpr int LDS_FLOATS = XS_FLOATS + MAXE + PMAX * MAXE + 16;
-
-DEV float2 ln_stats_reg(const float4 (&v)[U4], int n4, float* red) { return ln_stats_units<NT>(v, n4, red); }
 
 template <typename T>
 __global__ __launch_bounds__(NT) void rt_streams_kernel(const stgcn_rt_streams_desc d) {
@@ -69,34 +62,8 @@ __global__ __launch_bounds__(NT) void rt_streams_kernel(const stgcn_rt_streams_d
     }
   }
 
-  // input head: LayerNorm([3,1,V]) + fcn_in (rt_in_kernel's arithmetic)
-  {
-    float* xi = zs;
-    const int n = 3 * V, C0 = d.C0, ld = C0 + XPAD;
-    const float* x = d.x + b * n;
-    for (int i = tid; i < n; i += NT) xi[i] = x[i];
-    __syncthreads();
-    float s = 0.f;
-    for (int i = tid; i < n; i += NT) s += xi[i];
-    const float mean = block_sum(s, red) / (float)n;
-    float q = 0.f;
-    for (int i = tid; i < n; i += NT) {
-      const float t = xi[i] - mean;
-      q = fmaf(t, t, q);
-    }
-    const float rstd = 1.f / sqrtf(block_sum(q, red) / (float)(n - 1) + 1e-5f);
-    __syncthreads();
-    for (int i = tid; i < n; i += NT) xi[i] = fmaf(d.ln_w[i], (xi[i] - mean) * rstd, d.ln_b[i]);
-    __syncthreads();
-    for (int i = tid; i < V * C0; i += NT) {
-      const int v = i / C0, co = i - v * C0;
-      float t = d.b_in[co];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) t = fmaf(d.w_in[co * 3 + c], xi[c * V + v], t);
-      xs[v * ld + co] = t;
-    }
-    __syncthreads();
-  }
+  frame_head_in<NT>(d.x + b * 3 * V, V, d.C0, d.ln_w, d.ln_b, d.w_in, d.b_in, zs, red, xs, d.C0 + XPAD);
+  __syncthreads();
 
   for (int l = 0; l < d.L; ++l) {
     const stgcn_rt_streams_layer ly = d.layers[l];
@@ -114,31 +81,15 @@ __global__ __launch_bounds__(NT) void rt_streams_kernel(const stgcn_rt_streams_d
         const int p = res ? 0 : t2 / ntile, tile = res ? t2 : t2 - p * ntile;
         const T* panel = res ? static_cast<const T*>(ly.wrp) : static_cast<const T*>(ly.wp) + (long)p * ntile * nks * 512;
         panel += (long)tile * nks * 512;
-        float am[16];  // A_p[u = acc_row(r, lane)][v = row]
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int u = acc_row(r, lane);
-          am[r] = (!res && u < V && row < V) ? ly.A[(p * V + u) * V + row] : 0.f;
-        }
-        f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-        for (int kb = 0; kb < nks; kb += TU) {
-          typename Tr<T>::frag fa[TU], fb[TU];
-#pragma unroll
-          for (int u = 0; u < TU; ++u) fb[u] = load_b<T>(panel, kb + u, nks, lane);
-#pragma unroll
-          for (int u = 0; u < TU; ++u) fa[u] = load_a_as<T>(xs, ldx, kb + u, nks, row, h, V, Cin);
-#pragma unroll
-          for (int u = 0; u < TU; ++u) Tr<T>::mma(acc, fa[u], fb[u]);
-        }
+        float am[16];  // loaded ahead of the k-loop: in flight under it
+        amix_coeffs(ly.A, p, V, lane, !res, am);
+        f32x16 acc = conv_tile_acc<T, TU>(panel, xs, ldx, nks, row, h, V, Cin, lane);
         float* dst = rs;
         if (!res) {
           f32x16 z;
 #pragma unroll
           for (int r = 0; r < 16; ++r) z[r] = 0.f;
-#pragma unroll
-          for (int r = 0; r < 16; ++r) z = __builtin_amdgcn_mfma_f32_32x32x2f32(am[r], acc[r], z, 0, 0, 0);
+          amix_mma(am, acc, z);
           acc = z;
           dst = zs + p * E;
         }
@@ -177,9 +128,9 @@ __global__ __launch_bounds__(NT) void rt_streams_kernel(const stgcn_rt_streams_d
           if (ly.res_mode == 2) vr[j] = reinterpret_cast<const float4*>(rs)[e4];
         }
       }
-      const float2 st = ln_stats_reg(va, n4, red);
+      const float2 st = ln_stats_units<NT>(va, n4, red);
       float2 sr = make_float2(0.f, 1.f);
-      if (ly.res_mode == 2) sr = ln_stats_reg(vr, n4, red);
+      if (ly.res_mode == 2) sr = ln_stats_units<NT>(vr, n4, red);
       __syncthreads();  // every read of xs (the identity residual) before the overwrite
       const int ldy = Cout + XPAD;
 #pragma unroll
@@ -204,23 +155,8 @@ __global__ __launch_bounds__(NT) void rt_streams_kernel(const stgcn_rt_streams_d
     }
   }
 
-  // output head (rt_out_kernel's arithmetic)
-  {
-    const int C = d.layers[d.L - 1].Cout, ld = C + XPAD;
-    float* pool = zs;
-    for (int c = tid; c < C; c += NT) {
-      float s = 0.f;
-      for (int v = 0; v < V; ++v) s += xs[v * ld + c];
-      pool[c] = s / (float)V;
-    }
-    __syncthreads();
-    for (int k = w; k < d.K; k += NW) {  // one wave per class, the channels over the lanes
-      float s = 0.f;
-      for (int c = lane; c < C; c += 64) s = fmaf(d.w_out[(long)k * C + c], pool[c], s);
-      s = wave_sum(s);
-      if (lane == 0) out[k] = s + (d.b_out ? d.b_out[k] : 0.f);
-    }
-  }
+  const int C = d.layers[d.L - 1].Cout;
+  frame_head_out<NT>(xs, C + XPAD, V, C, d.w_out, d.b_out, d.K, zs, out);
 }
 
 template <typename T>

@@ -26,6 +26,7 @@ from .syncbn import active_sync
 from .graph import Graph
 from .modules import BatchNorm1d, LayerNorm, make_norm, resolve_dtype
 from .stgcn import IN_PAD
+from .streams import Keep, StreamBatch, f32, fill_heads, ln_rows, res_mode_of
 
 
 class OfflineLayer(nn.Module):
@@ -175,9 +176,8 @@ class OnlineLayer(nn.Module):
             a, r = K.rt_frame_gcn(x, A32, self.conv.weight.detach(), bias2d, ag.fifo, ag.accumulator, ag.idx,
                                   None if wr is None else wr.detach())
             n = self.bn_relu[0]
-            res_mode = 2 if self.is_residual_conv else (1 if self.is_residual else 0)
             rn = self.residual[1] if self.is_residual_conv else None
-            return K.rt_frame_norm(a, LF._flat_ln(n.weight), LF._flat_ln(n.bias), res_mode,
+            return K.rt_frame_norm(a, LF._flat_ln(n.weight), LF._flat_ln(n.bias), res_mode_of(self),
                                    r if self.is_residual_conv else (x if self.is_residual else None),
                                    None if rn is None else LF._flat_ln(rn.weight),
                                    None if rn is None else LF._flat_ln(rn.bias), ag.idx, ag.fifo_size, ag.stride)
@@ -189,7 +189,7 @@ class OnlineLayer(nn.Module):
         if self.is_residual_conv:
             wrp, cq, kq = resp
             r = K.conv_rows(x, wrp, Cin, Cout, cq, kq, 1, 1)
-        res_mode = 2 if self.is_residual_conv else (1 if self.is_residual else 0)
+        res_mode = res_mode_of(self)
         res = r if self.is_residual_conv else (x if self.is_residual else None)
         if self.normalization == "LayerNorm":
             st = K.ln_stats(a, 1, V, Cout)
@@ -323,19 +323,10 @@ class Model(nn.Module):
         """stgcn_rt_frame_desc of this model (K.L.RtFrameDesc) + the tensors it points to (kept alive with it)."""
         V = self.A.shape[-1]
         dev = self.A.device
-        keep = []
-
-        def p(t):
-            keep.append(t)
-            return t.data_ptr()
-
+        p = keep = Keep()
         d = K.L.RtFrameDesc()
         d.V, d.L, d.C0, d.K, d.blocks = V, len(self.st_gcn), self.fcn_in.out_channels, self.fcn_out.out_channels, 0
-        d.ln_w, d.ln_b = p(LF._flat_ln(self.norm_in.weight)), p(LF._flat_ln(self.norm_in.bias))
-        d.w_in = p(self.fcn_in.weight.detach().float().reshape(self.fcn_in.out_channels, -1).contiguous())
-        d.b_in = p(self.fcn_in.bias.detach().float().contiguous())
-        d.w_out = p(self.fcn_out.weight.detach().float().reshape(self.fcn_out.out_channels, -1).contiguous())
-        d.b_out = p(self.fcn_out.bias.detach().float().contiguous())
+        fill_heads(d, self, keep)
         d.sync = p(torch.zeros(4, dtype=torch.int32, device=dev))
         self._frame_status = torch.zeros(1, dtype=torch.int32, device=dev)
         d.status = p(self._frame_status)
@@ -345,19 +336,15 @@ class Model(nn.Module):
             A32, _, _, _, bias2d, _ = l._weights(Cin)
             y = d.layers[i]
             y.Cin, y.Cout, y.P, y.fifo_size, y.S = Cin, Cout, ag.A.shape[0], ag.fifo_size, ag.stride
-            y.res_mode = 2 if l.is_residual_conv else (1 if l.is_residual else 0)
-            y.A, y.w, y.bias2d = p(A32), p(l.conv.weight.detach().float().contiguous()), p(bias2d)
+            y.res_mode = res_mode_of(l)
+            y.A, y.w, y.bias2d = p(A32), p(f32(l.conv.weight)), p(bias2d)
             n = l.bn_relu[0]
-
-            def rows(t):  # LayerNorm([C,1,V]) affine (C,1,V) -> the rows' [V][C] layout
-                return t.detach().float().reshape(Cout, V).t().contiguous()
-
-            y.ln_w, y.ln_b = p(rows(n.weight)), p(rows(n.bias))
+            y.ln_w, y.ln_b = p(ln_rows(n.weight, Cout, V)), p(ln_rows(n.bias, Cout, V))
             y.fifo, y.acc, y.idx = p(ag.fifo), p(ag.accumulator), p(ag.idx)
             y.a_buf = p(torch.empty(V * Cout, dtype=torch.float32, device=dev))
             if l.is_residual_conv:
-                y.wr = p(l.residual[0].weight.detach().float().reshape(Cout, Cin).contiguous())
-                y.lnr_w, y.lnr_b = p(rows(l.residual[1].weight)), p(rows(l.residual[1].bias))
+                y.wr = p(f32(l.residual[0].weight).reshape(Cout, Cin))
+                y.lnr_w, y.lnr_b = p(ln_rows(l.residual[1].weight, Cout, V)), p(ln_rows(l.residual[1].bias, Cout, V))
                 y.r_buf = p(torch.empty(V * Cout, dtype=torch.float32, device=dev))
         return d, keep
 
@@ -395,7 +382,7 @@ class Model(nn.Module):
         return arch_conf
 
 
-class RtStreamBatch:
+class RtStreamBatch(StreamBatch):
     """B independent skeleton streams of one online LayerNorm rt-st-gcn (Model.stream_batch): every stream has its
     own FIFO, accumulators and indices for every layer, and ``step`` advances all of them by one frame in one launch
     (stgcn_rt_streams, rt_streams.hip: one workgroup per stream, no communication between workgroups).  ``dtype``
@@ -418,83 +405,49 @@ class RtStreamBatch:
                                "layers are out of scope)")
         if model.fcn_in.in_channels != 3:
             raise RuntimeError(f"stgcn_amd: stream_batch needs in_feat == 3, got {model.fcn_in.in_channels}")
-        if int(B) != B or B < 1:
-            raise RuntimeError(f"stgcn_amd: stream_batch needs B >= 1, got {B}")
-        V = model.A.shape[-1]
-        if not model._frame_desc_ok() or V * model.fcn_in.out_channels > 7680:
+        self._check_B(B)  # ahead of the shape limits, as every refusal's order was
+        if not model._frame_desc_ok() or model.A.shape[-1] * model.fcn_in.out_channels > 7680:
             raise RuntimeError("stgcn_amd: stream_batch shape limits: 2 <= V <= 32, channels % 4 == 0 and <= 256, "
                                f"V * C <= 7680, P <= 3, at most {K.L.RT_MAX_LAYERS} layers")
-        K.L.require_device(model.A)
-        self.model, self.B, self.V = model, int(B), V
-        dev = model.A.device
-        self.state = []  # per layer (fifo [B][fifo][V][C], acc [B][S][V][C], idx [B][2])
+        super().__init__(model, B)
+        V, dev = self.V, model.A.device
+        # state: per layer (fifo [B][fifo][V][C], acc [B][S][V][C], idx [B][2]), fp32 whatever dtype
         for l in model.st_gcn:
             ag = l.aggregate
             self.state.append((torch.zeros(self.B, ag.fifo_size, V, ag.out_channels, device=dev),
                                torch.zeros(self.B, ag.stride, V, ag.out_channels, device=dev),
                                torch.zeros(self.B, 2, dtype=torch.int32, device=dev)))
-        self.state_bytes = sum(t.numel() * t.element_size() for ts in self.state for t in ts)  # fp32 whatever dtype
-        self._all = torch.ones(self.B, dtype=torch.int32, device=dev)
-        self._pack = None
 
     def _desc(self):
         m = self.model
         key = m._param_key()
         if self._pack is not None and self._pack[0] == key:
             return self._pack[1]
-        V, keep = self.V, []
-
-        def p(t):
-            keep.append(t)
-            return t.data_ptr()
-
+        V = self.V
+        p = keep = Keep()
         d = K.L.RtStreamsDesc()
         d.V, d.L, d.C0, d.K, d.B = V, len(m.st_gcn), m.fcn_in.out_channels, m.fcn_out.out_channels, self.B
         d.dtype = K.L.dtype_code(self.dtype)
-        d.ln_w, d.ln_b = p(LF._flat_ln(m.norm_in.weight)), p(LF._flat_ln(m.norm_in.bias))
-        d.w_in = p(m.fcn_in.weight.detach().float().reshape(d.C0, -1).contiguous())
-        d.b_in = p(m.fcn_in.bias.detach().float().contiguous())
-        d.w_out = p(m.fcn_out.weight.detach().float().reshape(d.K, -1).contiguous())
-        d.b_out = p(m.fcn_out.bias.detach().float().contiguous())
+        fill_heads(d, m, keep)
         for i, l in enumerate(m.st_gcn):
             ag = l.aggregate
             Cin, Cout, P = l.conv.in_channels, ag.out_channels, ag.A.shape[0]
             A32, _, _, _, bias2d, _ = l._weights(Cin)
             y = d.layers[i]
             y.Cin, y.Cout, y.P, y.fifo_size, y.S = Cin, Cout, P, ag.fifo_size, ag.stride
-            y.res_mode = 2 if l.is_residual_conv else (1 if l.is_residual else 0)
+            y.res_mode = res_mode_of(l)
             y.A, y.bias2d = p(A32), p(bias2d)
             y.wp = p(K.rt_streams_pack_weight(l.conv.weight, P, self.dtype))
-
-            def rows(t):  # LayerNorm([C,1,V]) affine (C,1,V) -> the rows' [V][C] layout
-                return t.detach().float().reshape(Cout, V).t().contiguous()
-
             n = l.bn_relu[0]
-            y.ln_w, y.ln_b = p(rows(n.weight)), p(rows(n.bias))
+            y.ln_w, y.ln_b = p(ln_rows(n.weight, Cout, V)), p(ln_rows(n.bias, Cout, V))
             if l.is_residual_conv:
                 y.wrp = p(K.rt_streams_pack_weight(l.residual[0].weight, 1, self.dtype))
-                y.lnr_w, y.lnr_b = p(rows(l.residual[1].weight)), p(rows(l.residual[1].bias))
+                y.lnr_w, y.lnr_b = p(ln_rows(l.residual[1].weight, Cout, V)), p(ln_rows(l.residual[1].bias, Cout, V))
             y.fifo, y.acc, y.idx = (t.data_ptr() for t in self.state[i])
         self._pack = (key, (d, keep))
         return self._pack[1]
 
-    def step(self, x, active=None):
-        """x (B, 3, 1, V) -> (B, num_classes, 1).  ``active``: None (every stream steps), an int32 device tensor
-        [B] of codes (0 skip: state untouched, zero output row; 1 step; 2 restart then step) used as given with no
-        host sync, or a bool tensor / Python list converted on the host (True = step)."""
-        B, V = self.B, self.V
-        if x.dim() != 4 or tuple(x.shape) != (B, 3, 1, V):
-            raise RuntimeError(f"stgcn_amd: RtStreamBatch.step expects x of shape {(B, 3, 1, V)}, got {tuple(x.shape)}")
-        K.L.require_device(x)
-        x = K._f32c(x)
-        if active is None:
-            active = self._all
-        elif not (torch.is_tensor(active) and active.dtype == torch.int32 and active.is_cuda):
-            active = torch.as_tensor(active).to(device=x.device, dtype=torch.int32)
-        if tuple(active.shape) != (B,) or not active.is_contiguous():
-            raise RuntimeError(f"stgcn_amd: RtStreamBatch.step expects active of shape ({B},)")
-        d, _keep = self._desc()
-        out = torch.empty((B, d.K, 1), dtype=torch.float32, device=x.device)
+    def _launch(self, d, x, active, out):
         return K.rt_streams(d, x, active, out)
 
     def reset(self, streams=None):
