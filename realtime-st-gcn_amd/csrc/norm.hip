@@ -397,8 +397,10 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
   }
 }
 
-// S[w][c] += sum_f x[(f*V + w)][c] over the block's frames; thread item = (w, channel unit), registers
-// accumulate over frames, one atomicAdd per item per block.  period > 0: per-sample S[n][w][c].
+// S[w][c] += sum_f x[(f*V + w)][c].  Each block sums its fpb frames: thread item = (w, channel unit), registers
+// accumulate over the frames, and the block writes its [G][C] partial to its own slab of `part` (no atomics);
+// the launcher then adds the slabs into S in a fixed order (slab_sum_launch), so the result is bit-reproducible.
+// period > 0: per-sample S[n][w][c], blockIdx.y = sample, slabs [sample][block].
 template <typename T, int VEC>
 __global__ __launch_bounds__(256) void rowgroup_sum_kernel(const T* __restrict__ x, int ld, long F, int C, int G,
                                                            long fpb, long frames_per_sample, float* part) {
