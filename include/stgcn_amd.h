@@ -221,7 +221,12 @@ int stgcn_gconv_wgrad_finish(const float* dweff, const float* A, const float* W,
 
 /* BatchNorm with batch statistics (nn.BatchNorm2d(track_running_stats=False), stgcn.py:152,160,171;
  * BatchNorm1d input norm, models/utils/batchnorm.py:13-23 viewed as [N*T][V*C]).
- * Partials are float4 (count, mean, M2, 0) per (row block, channel); finalize merges them (fp64). */
+ * Partials are float4 (count, mean, M2, 0) per (row block, channel); finalize merges them (fp64).
+ * Row views (stgcn_bn_stats_partial, stgcn_bn_apply, stgcn_bn_bwd_reduce / _apply, stgcn_rowgroup_sum): 16-B
+ * units (8 bf16 / 4 fp32 channels) when C, every row stride and every base pointer are multiples of the unit,
+ * else one element at a time; STGCN_EBADSHAPE when a row does not fit 256 threads (C > 256 element-wise,
+ * C / unit > 256 otherwise).  stgcn_bn_apply_bits and the fused backward have no element-wise route: a view
+ * that rules out the 16-B units (stride or pointer) is STGCN_EBADSHAPE. */
 long stgcn_bn_stat_blocks(long M);
 int stgcn_bn_stats_partial(const void* x, int ld, long M, int C, void* part_f4, int dtype, void* stream);
 int stgcn_bn_finalize(const void* part_f4, int nblocks, int ld_part, int C, const float* gamma, const float* beta,

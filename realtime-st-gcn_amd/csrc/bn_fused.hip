@@ -316,10 +316,11 @@ Geo geo(long M, int C, int vec, long tb = 1024) {
 bool fits(const stgcn_bn_bwd_desc& a, int dtype, int& vec) {
   vec = dtype == 1 ? 8 : 4;
   if (a.C % vec || a.C / vec > 256 || a.C > 2048) return false;
-  auto al = [&](int ld) { return ld % vec == 0; };
+  // every row view read or written in 16-B units: stride a multiple of the unit, base pointer 16-B aligned
+  auto al = [&](const void* p, int ld) { return !p || (ld % vec == 0 && ((size_t)p & 15) == 0); };
   if (a.mask == 3 && dtype != 1) return false;
-  return al(a.lddy) && (!a.mask || a.mask == 3 || al(a.ldm)) && (!a.x1 || al(a.ldx1)) && (!a.x2 || al(a.ldx2)) &&
-         (!a.out1 || al(a.ldo1)) && (!a.out2 || al(a.ldo2));
+  return al(a.dy, a.lddy) && (!a.mask || a.mask == 3 || al(a.mref, a.ldm)) && al(a.x1, a.ldx1) &&
+         al(a.x2, a.ldx2) && al(a.out1, a.ldo1) && al(a.out2, a.ldo2);
 }
 
 long bn_bwd_fused_work_floats_impl(long M, int C, int dtype) {

@@ -13,6 +13,7 @@
 //    LN: dx = rstd*(gz - mean(gz) - xhat*sum(gz*xhat)/(F-1)), gz = dz*gamma.
 #include "common.h"
 #include "launchers.h"
+#include <initializer_list>
 #include <type_traits>
 
 namespace {
@@ -594,14 +595,15 @@ long rows_per_block(long M) {
 
 }  // namespace
 
-#define DISPATCH_VEC(dtype, C, ...)                                   \
+// vec: the width row_vec chose (8 / 4 elements of a 16-B unit, or 1)
+#define DISPATCH_VEC(dtype, vec, ...)                                 \
   if (dtype == 1) {                                                   \
     typedef bf16 T;                                                   \
-    if (C % 8 == 0) { constexpr int VEC = 8; __VA_ARGS__; }           \
+    if (vec == 8) { constexpr int VEC = 8; __VA_ARGS__; }             \
     else { constexpr int VEC = 1; __VA_ARGS__; }                      \
   } else {                                                            \
     typedef float T;                                                  \
-    if (C % 4 == 0) { constexpr int VEC = 4; __VA_ARGS__; }           \
+    if (vec == 4) { constexpr int VEC = 4; __VA_ARGS__; }             \
     else { constexpr int VEC = 1; __VA_ARGS__; }                      \
   }
 
@@ -613,16 +615,31 @@ long rows_per_block(long M) {
 
 long norm_stats_num_blocks(long M) { return (M + rows_per_block(M) - 1) / rows_per_block(M); }
 
-static bool rows_fit(int C, int dtype) {  // one row of C channels must fit the 256 threads
-  const int vec = dtype == 1 ? (C % 8 == 0 ? 8 : 1) : (C % 4 == 0 ? 4 : 1);
-  return C / vec <= 256;
+// Channels per load / store of the row kernels: a 16-B unit (8 bf16 / 4 fp32) when C, every row stride and every
+// base pointer allow it, else one element (the rule of ln.hip's vec_of and of bn_fused.hip's fits).  A null
+// pointer's stride is not read.
+struct RowView {
+  const void* p;
+  long ld;
+};
+static int row_vec(int dtype, int C, std::initializer_list<RowView> views) {
+  const int vec = dtype == 1 ? 8 : 4;
+  if (C % vec) return 1;
+  for (const RowView& v : views)
+    if (v.p && (v.ld % vec || ((size_t)v.p & 15))) return 1;
+  return vec;
+}
+
+static bool rows_fit(int C, int vec) {  // one row of C channels must fit the 256 threads (C <= 256 on the scalar route)
+  return C >= 1 && C / vec <= 256;
 }
 
 int bn_stats_partial_launch(const void* x, int ld, long M, int C, float4* part, int dtype, hipStream_t s) {
-  if (!rows_fit(C, dtype)) return STGCN_EBADSHAPE;
+  const int vec = row_vec(dtype, C, {{x, ld}});
+  if (!rows_fit(C, vec)) return STGCN_EBADSHAPE;
   const long rpb = rows_per_block(M);
   const int nb = (int)((M + rpb - 1) / rpb);
-  DISPATCH_VEC(dtype, C, hipLaunchKernelGGL((bn_stats_partial_kernel<T, VEC>), dim3(nb), dim3(256), 0, s,
+  DISPATCH_VEC(dtype, vec, hipLaunchKernelGGL((bn_stats_partial_kernel<T, VEC>), dim3(nb), dim3(256), 0, s,
                                             (const T*)x, ld, M, C, rpb, part));
   RET_HIP;
 }
@@ -648,12 +665,13 @@ int bn_merge_launch(const float4* part, int nb, int ldp, int C, float4* merged, 
 int bn_apply_launch(const void* u, int ldu, const float* sc, const float* sh, int res_mode, const void* r, int ldr,
                     const float* rsc, const float* rsh, int relu, void* y, int ldy, long M, int C, int dtype,
                     hipStream_t s, unsigned char* bits) {
-  if (!rows_fit(C, dtype)) return STGCN_EBADSHAPE;
+  const int vec = row_vec(dtype, C, {{u, ldu}, {res_mode ? r : nullptr, ldr}, {y, ldy}});
+  if (!rows_fit(C, vec)) return STGCN_EBADSHAPE;
   // bit-mask output: the 16-B (8 x bf16) path only
-  if (bits && (dtype != 1 || C % 8 || ldu % 8 || ldy % 8 || (res_mode && ldr % 8))) return STGCN_EBADSHAPE;
+  if (bits && (dtype != 1 || vec != 8)) return STGCN_EBADSHAPE;
   const long rpb = elt_rows_per_block(M);
   const int nb = (int)((M + rpb - 1) / rpb);
-  DISPATCH_VEC(dtype, C, hipLaunchKernelGGL((bn_apply_kernel<T, VEC>), dim3(nb), dim3(256), 0, s,
+  DISPATCH_VEC(dtype, vec, hipLaunchKernelGGL((bn_apply_kernel<T, VEC>), dim3(nb), dim3(256), 0, s,
                                             (const T*)u, ldu, sc, sh, res_mode, (const T*)r, ldr, rsc, rsh, relu,
                                             (T*)y, ldy, M, C, rpb, bits));
   RET_HIP;
@@ -662,10 +680,11 @@ int bn_apply_launch(const void* u, int ldu, const float* sc, const float* sh, in
 int bn_bwd_reduce_launch(const void* dy, int lddy, int mask, const void* mref, int ldm, const float* msc,
                          const float* msh, const void* x, int ldx, const float2* mean_rstd, long M, int C,
                          float2* part, float2* out, int dtype, hipStream_t s) {
-  if (!rows_fit(C, dtype)) return STGCN_EBADSHAPE;
+  const int vec = row_vec(dtype, C, {{dy, lddy}, {mask ? mref : nullptr, ldm}, {x, ldx}});
+  if (!rows_fit(C, vec)) return STGCN_EBADSHAPE;
   const long rpb = rows_per_block(M);
   const int nb = (int)((M + rpb - 1) / rpb);
-  DISPATCH_VEC(dtype, C, hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, VEC>), dim3(nb), dim3(256), 0, s,
+  DISPATCH_VEC(dtype, vec, hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, VEC>), dim3(nb), dim3(256), 0, s,
                                             (const T*)dy, lddy, mask, (const T*)mref, ldm, msc, msh, (const T*)x,
                                             ldx, mean_rstd, M, C, rpb, part));
   hipLaunchKernelGGL(sum_partials_kernel, dim3(C), dim3(256), 0, s, part, nb, C, out);
@@ -676,10 +695,11 @@ int bn_bwd_apply_launch(const void* dy, int lddy, int mask, const void* mref, in
                         const float* msh, const void* x, int ldx, const float2* mean_rstd, const float* gamma,
                         const float2* sums, long M, int C, void* dx, int lddx, int accumulate, int dtype,
                         hipStream_t s) {
-  if (!rows_fit(C, dtype)) return STGCN_EBADSHAPE;
+  const int vec = row_vec(dtype, C, {{dy, lddy}, {mask ? mref : nullptr, ldm}, {x, ldx}, {dx, lddx}});
+  if (!rows_fit(C, vec)) return STGCN_EBADSHAPE;
   const long rpb = elt_rows_per_block(M);
   const int nb = (int)((M + rpb - 1) / rpb);
-  DISPATCH_VEC(dtype, C, hipLaunchKernelGGL((bn_bwd_apply_kernel<T, VEC>), dim3(nb), dim3(256), 0, s,
+  DISPATCH_VEC(dtype, vec, hipLaunchKernelGGL((bn_bwd_apply_kernel<T, VEC>), dim3(nb), dim3(256), 0, s,
                                             (const T*)dy, lddy, mask, (const T*)mref, ldm, msc, msh, (const T*)x,
                                             ldx, mean_rstd, gamma, sums, M, C, (T*)dx, lddx, accumulate, rpb));
   RET_HIP;
@@ -712,7 +732,8 @@ int rowgroup_sum_launch(const void* x, int ld, long M, int C, int G, long period
   long F, fps, nsamp, fpb;
   int nb;
   rowgroup_geometry(M, G, period, F, fps, nsamp, fpb, nb);
-  DISPATCH_VEC(dtype, C, hipLaunchKernelGGL((rowgroup_sum_kernel<T, VEC>), dim3(nb, (unsigned)nsamp), dim3(256), 0, s,
+  const int vec = row_vec(dtype, C, {{x, ld}});
+  DISPATCH_VEC(dtype, vec, hipLaunchKernelGGL((rowgroup_sum_kernel<T, VEC>), dim3(nb, (unsigned)nsamp), dim3(256), 0, s,
                                             (const T*)x, ld, F, C, G, fpb, fps, work));
   const long E = (long)G * C;
   slab_sum_launch(work, nsamp, nb, E, work + (long)nb * nsamp * E, S, 1, s);  // fixed-order, two levels
