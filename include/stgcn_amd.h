@@ -38,7 +38,8 @@ extern "C" {
  *      still 7: stgcn_co_streams* added (co_streams.hip) — additive likewise;
  *      still 7: stgcn_rt_streams_desc.pad_ became dtype (0 = fp32, what a zero-filled descriptor always passed; 1 = bf16
  *      conv operands), stgcn_rt_streams_layer.wp / wrp became const void* of that element type, and
- *      stgcn_rt_streams_pack_weight_as was added — no size, offset or existing entry point changed. */
+ *      stgcn_rt_streams_pack_weight_as was added — no size, offset or existing entry point changed;
+ *      still 7: stgcn_co_clip* added (co_clip.hip) — additive likewise. */
 #define STGCN_ABI_VERSION 7
 
 /* Implicit-GEMM (Kt x 1) row convolution; see conv_rows.hip for the exact contract.
@@ -659,6 +660,84 @@ typedef struct {
 int stgcn_co_streams_splits(const stgcn_co_streams_desc* d, int layer);
 long stgcn_co_streams_workspace(const stgcn_co_streams_desc* d, int layer);
 int stgcn_co_streams(const stgcn_co_streams_desc* d, void* stream);
+
+/* CoST-GCN clip inference (co_clip.hip): T consecutive frames of ONE stream per call, on the rings stgcn_co_layer's
+ * calls use (ring, res_ring, idx: the same buffers, the same layout).  The contract:
+ *   1. out[t] is what the per-frame calls would give for frame t, the T frames fed one at a time from the state the
+ *      rings hold on entry (equal within rounding: the sums below have an order of their own);
+ *   2. on return the rings and idx are what those T calls would have left: new frame t in ring slot
+ *      (idx0 - 1 - t) mod fifo, its residual row in res_ring slot (idx1 - 1 - t) mod R, idx moved by -T (mod fifo, R);
+ *   3. per-frame calls, clips of any T and a re-initialisation of the rings by the caller can be mixed on one stream.
+ * Per clip: an input head and an output head per frame, and per layer five launches, every hand-off a kernel boundary,
+ * no atomics, no workgroup waiting on another:
+ *   gcn    : z_buf[t], r_buf[t] as stgcn_co_streams computes them for a stream (packed wp / wrp)
+ *   push   : hist[fifo-1+t] = ReLU(LN1(z_buf[t])) (dtype elements), resq[Kt/2+t] = the residual row of frame t; the
+ *            same launch copies the fifo-1 newest ring frames and the Kt/2 newest res_ring rows, oldest first, into
+ *            hist[0 .. fifo-1) and resq[0 .. Kt/2).  It is the only launch that reads the rings and writes none.
+ *   taps   : partial[t][s][v][co] = sum over K split s of wt . hist, tap k of frame t = hist[fifo-1 + t - k*S]: one
+ *            GEMM with T*V dense rows; a workgroup holds 4 row tiles of 32 against one load of each weight fragment
+ *   finish : y[t] = relu(LN2(bt + sum_s partial[t][s]) + resq[t]); idx advanced
+ *   state  : the last min(T, fifo) hist frames and min(T, Kt/2+1) resq rows into their ring slots.  It is the only
+ *            launch that writes the rings, and it runs after the taps and finish launches: a new frame never replaces
+ *            a carried frame that an earlier frame of the clip still has to read.
+ * Order of every sum: the 16-element k-steps of a K split in sequence within a wave (with Cout < 256 the 8 / (Cout/32)
+ * waves of a column tile interleave the split's k-steps and are summed in index order), then the splits in index
+ * order, then bt; LayerNorm statistics as in the per-frame calls (two passes, 1024 threads, fixed order).  The split
+ * count is a function of (Cout, Kt) alone (stgcn_co_clip_splits; layers[l].splits > 0 forces it), never of T or the
+ * device.  Hence chunk invariance: a clip of T frames and any split of it into consecutive clips (T = 1 included)
+ * give the same bits in out, ring, res_ring and idx; a captured graph of a clip replays bit-identically.
+ * x: the (3, T, V) fp32 clip, channel c of frame t at x[c * x_stride + t * V] (x_stride >= T * V: a dense clip has
+ * x_stride = T * V, a chunk of a longer clip keeps the whole clip's stride).  out: [T][K].
+ * wt: stgcn_co_pack_weight's image; wp / wrp: stgcn_rt_streams_pack_weight's (groups = P / 1), fp32.
+ * dtype 0 fp32 | 1 bf16: the element type of wt, ring and hist only.
+ * Limits per layer are stgcn_co_layer's, layers[l].Cin == layers[l-1].Cout (C0 for l = 0), 1 <= L <=
+ * STGCN_RT_MAX_LAYERS, K >= 1, 1 <= T <= STGCN_CO_CLIP_MAX_T (longer clips: consecutive calls).  Anything else, or a
+ * NULL required pointer, returns 1 (2 for the dtype) before any launch; the two queries return -1.  The scratch
+ * buffers of different layers may alias each other (each is dead once its layer's state launch has run), except y of
+ * neighbouring layers. */
+#define STGCN_CO_CLIP_MAX_T 256
+typedef struct {
+  int Cin, Cout, P, Kt, S, res_mode, splits, pad_;
+  const float* A;       /* [P][V][V] graph * importance */
+  const float* wp;      /* packed gcn.conv weight, P * stgcn_rt_streams_pack_elems(Cout, Cin) floats */
+  const float* bias2d;  /* [V][Cout] or NULL */
+  const float* wrp;     /* packed residual.0 weight (res_mode 2) */
+  const float* br;      /* [Cout] or NULL */
+  const float* ln1_w;   /* tcn.0, (C,1,V) as stored */
+  const float* ln1_b;
+  const float* ln2_w;   /* tcn.3 */
+  const float* ln2_b;
+  const float* lnr_w;   /* residual.1 (res_mode 2) */
+  const float* lnr_b;
+  const void* wt;       /* packed tcn.2 weight, dtype elements */
+  const float* bt;      /* [Cout] tcn.2 bias or NULL */
+  void* ring;           /* [fifo][V][Cout] dtype elements: the stream's state, as in stgcn_co_layer */
+  float* res_ring;      /* [Kt/2+1][V][Cout] */
+  int* idx;             /* int[2] */
+  float* z_buf;         /* [T][V][Cout] scratch */
+  float* r_buf;         /* [T][V][Cout] scratch (res_mode 2) */
+  void* hist;           /* [fifo-1 + T][V][Cout] scratch, dtype elements */
+  float* resq;          /* [Kt/2 + T][V][Cout] scratch */
+  float* partial;       /* [T][splits][V][Cout] scratch */
+  float* y;             /* [T][V][Cout] the layer's output rows */
+} stgcn_co_clip_layer;
+typedef struct {
+  int T, V, L, C0, K, dtype;
+  long x_stride;        /* elements between two channels of x */
+  const float* x;       /* the clip, see above */
+  const float* ln_w;    /* [3*V] */
+  const float* ln_b;
+  const float* w_in;    /* [C0][3] */
+  const float* b_in;    /* [C0] */
+  const float* w_out;   /* [K][C_last] */
+  const float* b_out;   /* [K] or NULL */
+  float* h0;            /* [T][V][C0] scratch: the first layer's input rows */
+  float* out;           /* [T][K] */
+  stgcn_co_clip_layer layers[STGCN_RT_MAX_LAYERS];
+} stgcn_co_clip_desc;
+int stgcn_co_clip_splits(const stgcn_co_clip_desc* d, int layer);
+long stgcn_co_clip_workspace(const stgcn_co_clip_desc* d, int layer);  /* bytes of layers[layer].partial */
+int stgcn_co_clip(const stgcn_co_clip_desc* d, void* stream);
 
 /* MS-TCN stage (models/mstcn/mstcn.py:68-116; ms_stage.hip): SingleStage = conv_in 1x1, num_layers
  * DilatedResidualLayers (dilation 2^i), conv_out 1x1, forward and backward, batch 1.  Activations are fp32 rows

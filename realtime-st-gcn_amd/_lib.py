@@ -135,6 +135,22 @@ class CoStreamsDesc(ctypes.Structure):  # stgcn_co_streams_desc
                [("layers", CoStreamsLayer * RT_MAX_LAYERS)]
 
 
+CO_CLIP_MAX_T = 256  # STGCN_CO_CLIP_MAX_T
+
+
+class CoClipLayer(ctypes.Structure):  # stgcn_co_clip_layer
+    _fields_ = [(n, c_int) for n in ("Cin", "Cout", "P", "Kt", "S", "res_mode", "splits", "pad_")] + \
+               [(n, c_void_p) for n in ("A", "wp", "bias2d", "wrp", "br", "ln1_w", "ln1_b", "ln2_w", "ln2_b", "lnr_w",
+                                        "lnr_b", "wt", "bt", "ring", "res_ring", "idx", "z_buf", "r_buf", "hist",
+                                        "resq", "partial", "y")]
+
+
+class CoClipDesc(ctypes.Structure):  # stgcn_co_clip_desc
+    _fields_ = [(n, c_int) for n in ("T", "V", "L", "C0", "K", "dtype")] + [("x_stride", c_long)] + \
+               [(n, c_void_p) for n in ("x", "ln_w", "ln_b", "w_in", "b_in", "w_out", "b_out", "h0", "out")] + \
+               [("layers", CoClipLayer * RT_MAX_LAYERS)]
+
+
 class MsLayer(ctypes.Structure):  # stgcn_ms_layer
     _fields_ = [(n, c_int) for n in ("R", "V", "F", "dil", "dtype", "pad_")] + \
                [(n, c_void_p) for n in ("x", "wp", "b1", "b2", "y", "h", "dy", "g", "dx", "part", "grads")]
@@ -240,6 +256,9 @@ _SIGS = {
     "stgcn_co_streams_splits": (c_int, [ctypes.POINTER(CoStreamsDesc), c_int]),
     "stgcn_co_streams_workspace": (c_long, [ctypes.POINTER(CoStreamsDesc), c_int]),
     "stgcn_co_streams": (c_int, [ctypes.POINTER(CoStreamsDesc), c_void_p]),
+    "stgcn_co_clip_splits": (c_int, [ctypes.POINTER(CoClipDesc), c_int]),
+    "stgcn_co_clip_workspace": (c_long, [ctypes.POINTER(CoClipDesc), c_int]),
+    "stgcn_co_clip": (c_int, [ctypes.POINTER(CoClipDesc), c_void_p]),
     "stgcn_ms_pack_elems": (c_long, [c_int]),
     "stgcn_ms_pack_layer": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
     "stgcn_ms_wgrad_blocks": (c_int, [c_int]),

@@ -17,6 +17,11 @@ restarts the stream.  ``reset_state()`` restarts it explicitly and keeps the buf
 Scope: LayerNorm only (the reference's BatchNorm variant takes statistics over whatever the FIFO holds), batch 1,
 inference only, in_feat 3, V <= 32, P <= 3, channels % 4 == 0 and <= 256, odd Kt <= 69, stride 1 or 2.
 
+``forward_clip(x (1, in_feat, T, V)) -> (1, num_classes, T)`` advances the same stream by T frames in one call
+(co_clip.hip): every layer's temporal conv becomes one GEMM with T*V rows that reads the tap weights once per clip.
+Its columns and the state it leaves are those of T ``forward`` calls within rounding, and bit for bit those of any
+other chunking of the same frames through ``forward_clip``.
+
 ``Model.stream_batch(B)`` serves B independent streams per call (CoStreamBatch, co_streams.hip) with state of its own;
 ``forward`` stays the call for one stream.
 """
@@ -110,6 +115,7 @@ class Model(nn.Module):
         self.fcn_out = nn.Conv2d(conf["out_ch"][-1], out_channels=kwargs["num_classes"], kernel_size=1)
         self.compute_dtype = torch.float32
         self.k_splits = 0  # stgcn_co_layer.splits of every layer: 0 = the library's choice (tests force others)
+        self.clip_chunk = 256  # forward_clip runs longer clips in chunks of this many frames (<= STGCN_CO_CLIP_MAX_T)
         self._plan = None  # (key, _Plan): descriptors, weight packs and ring state; never part of the state_dict
 
     # ------------------------------------------------------------------ whatever may change a parameter drops the plan
@@ -230,6 +236,81 @@ class Model(nn.Module):
             raise RuntimeError("stgcn_amd: co-st-gcn processes one frame of batch 1: x (1, in_feat, 1, V), got "
                                f"{tuple(x.shape)}")
         return self._frame(x)
+
+    # ------------------------------------------------------------------ clips: T frames per call on the same rings
+    def _clip_desc(self, plan, T):
+        """The stgcn_co_clip_desc for a clip of T <= clip_chunk frames: the plan's own rings, tap packs and norm
+        affines, plus scratch for the next power of two >= T (capped at clip_chunk), shared by every layer.  One
+        descriptor per capacity is kept with the plan, so a captured graph of a clip keeps its buffers."""
+        cap = min(int(self.clip_chunk), 1 << (T - 1).bit_length())
+        clips = plan.setdefault("clips", {})
+        if cap in clips:
+            return clips[cap][0]
+        dev, dt = self.A.device, self.compute_dtype
+        V, P, layers = self.A.shape[-1], self.A.shape[0], self.gcn_networks
+        with K.device_of(self.A):
+            if "clip_packs" not in plan:  # the graph conv as co_streams.hip packs it, once per plan
+                plan["clip_packs"] = [(K.rt_streams_pack_weight(l.gcn.conv.weight, P),
+                                       K.rt_streams_pack_weight(l.residual[0].weight, 1) if l.is_residual_conv else None)
+                                      for l in layers]
+            d = K.L.CoClipDesc()
+            d.T, d.V, d.L, d.C0, d.K = cap, V, len(layers), self.fcn_in.out_channels, self.fcn_out.out_channels
+            d.dtype = K.L.dtype_code(dt)
+            for y, c in zip(d.layers, plan["descs"]):
+                y.Cin, y.Cout, y.P, y.Kt, y.S, y.res_mode, y.splits = c.Cin, c.Cout, c.P, c.Kt, c.S, c.res_mode, self.k_splits
+            nbytes = []
+            for i in range(d.L):
+                d.layers[i].splits, nb = K.co_clip_workspace(d, i)
+                nbytes.append(nb)
+            p = keep = Keep()
+            fill_heads(d, self, keep)
+            cmax = max(l.out_channels for l in layers)
+
+            def buf(n, dtype=torch.float32):
+                return p(torch.empty(n, dtype=dtype, device=dev))
+
+            d.h0 = buf(cap * V * d.C0)
+            z, r, ys = buf(cap * V * cmax), buf(cap * V * cmax), (buf(cap * V * cmax), buf(cap * V * cmax))
+            hist = buf(max((l.fifo_size - 1 + cap) * V * l.out_channels for l in layers), dt)
+            resq = buf(max((l.gamma // 2 + cap) * V * l.out_channels for l in layers))
+            partial = p(K._workspace(max(nbytes), dev))
+            for i, (y, c) in enumerate(zip(d.layers, plan["descs"])):
+                for n in ("A", "bias2d", "br", "ln1_w", "ln1_b", "ln2_w", "ln2_b", "lnr_w", "lnr_b", "wt", "bt", "ring",
+                          "res_ring", "idx"):
+                    setattr(y, n, getattr(c, n))
+                wp, wrp = plan["clip_packs"][i]
+                y.wp, y.wrp = wp.data_ptr(), K.L.ptr(wrp)
+                y.z_buf, y.r_buf, y.hist, y.resq, y.partial, y.y = z, r, hist, resq, partial, ys[i & 1]
+        clips[cap] = (d, keep)
+        return d
+
+    def forward_clip(self, x):
+        """x (1, in_feat, T, V), T >= 1 -> (1, num_classes, T) fp32: column t is what ``forward`` would return for
+        frame t, the frames fed one at a time from the stream's current state, and the state afterwards is what those
+        T calls would have left (stgcn_co_clip, co_clip.hip: every layer's temporal conv as one GEMM over the clip).
+        ``forward``, ``forward_clip`` and ``reset_state()`` mix freely on one stream.  Clips longer than ``clip_chunk``
+        frames run in chunks; any chunking, T = 1 pieces included, gives the same bits."""
+        if torch.is_grad_enabled() and any(q.requires_grad for q in self.parameters()):
+            raise RuntimeError("stgcn_amd: co-st-gcn is inference only (call under torch.no_grad() or freeze the "
+                               "parameters)")
+        if x.dim() != 4 or x.shape[0] != 1 or x.shape[1] != self.fcn_in.in_channels or x.shape[2] < 1 or \
+                x.shape[3] != self.A.shape[-1]:
+            raise RuntimeError("stgcn_amd: co-st-gcn processes a clip of batch 1: x (1, in_feat, T >= 1, V), got "
+                               f"{tuple(x.shape)}")
+        chunk = int(self.clip_chunk)
+        if not 1 <= chunk <= K.L.CO_CLIP_MAX_T:
+            raise RuntimeError(f"stgcn_amd: co-st-gcn clip_chunk must be in [1, {K.L.CO_CLIP_MAX_T}], got {chunk}")
+        K.L.require_device(x)
+        with torch.no_grad():
+            plan, _ = self._ensure()
+            x = K._f32c(x)
+            T = x.shape[2]
+            out = torch.empty((T, self.fcn_out.out_channels), dtype=torch.float32, device=x.device)
+            with K.device_of(x):
+                for t0 in range(0, T, chunk):
+                    n = min(chunk, T - t0)
+                    K.co_clip(self._clip_desc(plan, n), x, t0, n, out)
+        return out.t().unsqueeze(0)
 
     def stream_batch(self, B, splits=0):
         """B independent skeleton streams of this model, advanced together one frame per call (CoStreamBatch,

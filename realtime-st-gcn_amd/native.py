@@ -1094,6 +1094,26 @@ def co_streams(desc, x, active, out):
     return out
 
 
+def co_clip_workspace(desc, layer):
+    """(K-split count, bytes of the split partials) of layer ``layer`` of a stgcn_co_clip_desc (shapes and T filled
+    in); raises on shapes the kernels do not take."""
+    n = L.lib().stgcn_co_clip_splits(ctypes.byref(desc), layer)
+    nbytes = L.lib().stgcn_co_clip_workspace(ctypes.byref(desc), layer)
+    if n < 1 or nbytes < 0:
+        raise RuntimeError("stgcn_amd: co-st-gcn clip shape not supported (V <= 32, P <= 3, C % 4 == 0, C <= 256, odd "
+                           f"Kt <= 69, stride 1 or 2, at most {L.RT_MAX_LAYERS} layers, 1 <= T <= {L.CO_CLIP_MAX_T})")
+    return n, nbytes
+
+
+def co_clip(desc, x, t0, T, out):
+    """Frames t0 .. t0+T-1 of the clip x (1, 3, T_all, V) fp32 dense through a CoST-GCN stream (stgcn_co_clip):
+    rows t0 .. t0+T-1 of out (T_all, K); ``desc`` is the model's stgcn_co_clip_desc (costgcn.Model)."""
+    V = x.shape[3]
+    desc.T, desc.x_stride = T, x.shape[2] * V
+    desc.x, desc.out = x.data_ptr() + 4 * t0 * V, out.data_ptr() + 4 * t0 * out.shape[1]
+    L.check(L.lib().stgcn_co_clip(ctypes.byref(desc), L.stream()), "co_clip")
+
+
 # ------------------------------------------------------------------------------ MS-TCN stage (ms_stage.hip)
 MS_MODES = {"logits": 0, "logsoftmax": 1, "softmax": 2}  # the `refine` / `output_type` selectors
 

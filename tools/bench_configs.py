@@ -26,6 +26,10 @@ ms:       MS-TCN refinement stage (F = 64, 10 layers, 52 classes, L = 2000; ms_s
 co_streams: co-st-gcn as a stream batch (Model.stream_batch, stgcn_co_streams) at Kt in {9, 69} x {fp32, bf16} x
           B in {1, 8, 64, 256}: one tick captured as a HIP graph, HIP-event device time over 200 replays after the
           rings filled, beside the single-stream route graph-replayed in the same run.  Only with --only co_streams.
+co_clip:  co-st-gcn clip inference (Model.forward_clip, stgcn_co_clip) at Kt in {9, 69} x {fp32, bf16} x T in {1, 4,
+          16, 64, 256}: device ms per captured clip and per frame, rings filled, beside the per-frame route
+          graph-replayed in the same run in alternating windows; rows appended to profiles/co_clip.jsonl.  Only with
+          --only co_clip.
 streams:  config 3 as a stream batch (Model.stream_batch, stgcn_rt_streams): B in {1, 8, 64, 256, 1024} streams
           advanced one frame per launch, HIP-event device time over 200 graph-replayed ticks after the FIFOs have
           filled, beside the single-stream one-launch route (stgcn_rt_frame) graph-replayed in the same run: ms per
@@ -33,7 +37,7 @@ streams:  config 3 as a stream batch (Model.stream_batch, stgcn_rt_streams): B i
           bf16) are measured in the same process, interleaved per B, --stream-repeats times over; the rows are also
           appended to profiles/rt_streams.jsonl.  Only with --only streams.
 
-    python tools/bench_configs.py [--frames 2000] [--steps 10] [--only 3|5|ln|f1|co|ms|streams|co_streams]
+    python tools/bench_configs.py [--frames 2000] [--steps 10] [--only 3|5|ln|f1|co|ms|streams|co_streams|co_clip]
 Prints one JSON line per config.
 """
 import argparse
@@ -457,6 +461,80 @@ def co_streams(P, dev, kernel, dtype, batches=(1, 8, 64, 256)):
     return rows
 
 
+def _capture(step):
+    step()  # descriptors, packs and buffers outside the capture
+    g = torch.cuda.CUDAGraph()
+    s_ = torch.cuda.Stream()
+    s_.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s_):
+        with torch.cuda.graph(g):
+            step()
+    torch.cuda.current_stream().wait_stream(s_)
+    return g
+
+
+def _timed(g, reps):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        g.replay()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+def co_clip(P, dev, kernel, dtype, Ts=(1, 4, 16, 64, 256), repeats=3):
+    """Rows of the co-st-gcn clip table: the reference schedule at temporal kernel ``kernel`` in ``dtype``, one
+    forward_clip of T frames captured as a HIP graph, beside the per-frame route graph-replayed in the same run.  Both
+    act on the same stream with its rings filled; the timed windows alternate (per-frame, every T) ``repeats`` times and
+    each row gives the median and the min / max of its windows."""
+    arch = {"strategy": "spatial", "in_feat": 3, "stages": 1, "kernel": kernel, "output_type": "logits",
+            "normalization": "LayerNorm", "num_classes": 52, "graph": P.PKU_MMD,
+            "st-gcn": dict(LAYERS, kernel=kernel, latency=False, importance=True, in_feat=3, stages=1,
+                           dilation=[1] * 9)}
+    torch.manual_seed(0)
+    m = P.MODELS["co-st-gcn"](rank=None, **arch).to(dev).eval().set_compute_dtype(dtype)
+    fill = max(arch["st-gcn"]["stride"]) * (kernel - 1) + 1
+    gen = torch.Generator(device=dev).manual_seed(3)
+    es = 2 if dtype == "bf16" else 4
+    wbytes = sum(kernel * c * c * es for c in LAYERS["out_ch"])
+    with torch.no_grad():
+        x1 = torch.randn(1, 3, 1, 25, device=dev, generator=gen)
+        xs = {T: torch.randn(1, 3, T, 25, device=dev, generator=gen) for T in Ts}
+        frame = _capture(lambda: m(x1))
+        clip = {T: _capture(lambda T=T: m.forward_clip(xs[T])) for T in Ts}
+        for _ in range(fill):
+            frame.replay()
+        reps = {T: max(10, 512 // T) for T in Ts}  # at least 512 frames per window
+        for T in Ts:  # every shape once before a timed window
+            clip[T].replay()
+        t_frame, t_clip = [], {T: [] for T in Ts}
+        for _ in range(repeats):
+            t_frame.append(_timed(frame, 500))
+            for T in Ts:
+                t_clip[T].append(_timed(clip[T], reps[T]))
+    med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
+    d = m._clip_desc(m._plan[1], 1)
+    rows = []
+    for T in Ts:
+        ms = med(t_clip[T])
+        rows.append({"config": "co-st-gcn clip inference (stgcn_co_clip), ln/costgcn_local.json widths, "
+                               f"Kt={kernel}: one clip of T frames on one stream",
+                     "dtype": dtype, "Kt": kernel, "T": T, "clip_device_ms": round(ms, 4),
+                     "clip_device_ms_min_max": [round(min(t_clip[T]), 4), round(max(t_clip[T]), 4)],
+                     "clip_ms_per_frame": round(ms / T, 5),
+                     "per_frame_route_ms_per_frame": round(med(t_frame), 4),
+                     "per_frame_route_ms_min_max": [round(min(t_frame), 4), round(max(t_frame), 4)],
+                     "ratio_per_frame_over_clip": round(med(t_frame) / (ms / T), 2),
+                     "ratio_min_max": [round(min(t_frame) / (max(t_clip[T]) / T), 2),
+                                       round(max(t_frame) / (min(t_clip[T]) / T), 2)],
+                     "frames_per_s": round(T / ms * 1e3, 1), "k_splits": [d.layers[i].splits for i in range(9)],
+                     "launches_per_clip": 2 + 5 * 9, "tap_weight_bytes": wbytes,
+                     "note": f"HIP events around graph replays ({reps[T]} clips, 500 frames per window), {repeats} "
+                             "alternating windows, rings filled; no per-kernel trace"})
+    return rows
+
+
 MS_TCN = {"latency": False, "importance": True, "stages": 3, "layers": [10, 10, 10], "kernel": [3, 3, 3],
           "filters": [64, 64, 64], "dropout": [0, 0, 0]}
 MSGCN_ARCH = {"strategy": "spatial", "receptive_field": 50, "segment": 2000, "in_feat": 3, "stages": 4,
@@ -604,6 +682,13 @@ def main():
             for dtype in ("fp32", "bf16"):
                 for row in co_streams(P, dev, kernel, dtype):
                     print(json.dumps(row), flush=True)
+    if args.only == "co_clip":
+        with open(os.path.join(ROOT, "profiles", "co_clip.jsonl"), "a") as f:
+            for kernel in (9, 69):
+                for dtype in ("fp32", "bf16"):
+                    for row in co_clip(P, dev, kernel, dtype):
+                        print(json.dumps(row), flush=True)
+                        f.write(json.dumps(row) + "\n")
     if args.only == "co":
         for kernel in (9, 69):
             for dtype in ("fp32", "bf16"):
