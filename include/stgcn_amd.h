@@ -39,7 +39,8 @@ extern "C" {
  *      still 7: stgcn_rt_streams_desc.pad_ became dtype (0 = fp32, what a zero-filled descriptor always passed; 1 = bf16
  *      conv operands), stgcn_rt_streams_layer.wp / wrp became const void* of that element type, and
  *      stgcn_rt_streams_pack_weight_as was added — no size, offset or existing entry point changed;
- *      still 7: stgcn_co_clip* added (co_clip.hip) — additive likewise. */
+ *      still 7: stgcn_co_clip* added (co_clip.hip) — additive likewise;
+ *      still 7: stgcn_co_streams_clip* added (co_streams_clip.hip) — additive likewise. */
 #define STGCN_ABI_VERSION 7
 
 /* Implicit-GEMM (Kt x 1) row convolution; see conv_rows.hip for the exact contract.
@@ -738,6 +739,76 @@ typedef struct {
 int stgcn_co_clip_splits(const stgcn_co_clip_desc* d, int layer);
 long stgcn_co_clip_workspace(const stgcn_co_clip_desc* d, int layer);  /* bytes of layers[layer].partial */
 int stgcn_co_clip(const stgcn_co_clip_desc* d, void* stream);
+
+/* CoST-GCN clip inference for B independent streams (co_streams_clip.hip): one call advances stream b by n_b frames,
+ * on the stream-major state of stgcn_co_streams (ring [B][fifo][V][Cout], res_ring [B][Kt/2+1][V][Cout], idx [B][2]:
+ * the same buffers, so per-frame ticks and clips mix on one batch).  Per stream it is stgcn_co_clip: the same stages,
+ * the same order of every sum, the same split counts (stgcn_co_streams_clip_splits: a function of (Cout, Kt) and
+ * layers[l].splits alone, never of B, T or t0), so a stream's out, ring, res_ring and idx are bit-identical to
+ * stgcn_co_clip's on the same frames from the same state, whatever B, its slot, T, the other streams' codes, lengths
+ * and contents, and however the frames are split into consecutive calls.
+ * active [B] and lengths [B] are device int32, read by the kernels (a captured call replays with other values):
+ *   n_b = clamp(lengths[b] - t0, 0, T) frames are consumed, frames 0 .. n_b-1 of this call's T;
+ *   code 0: skip — state untouched, no ring reads, every out row of the stream zero;
+ *   code 2 and t0 == 0: restart, then advance — the carried history is the empty FIFO (ReLU(ln1_b) rows, zero residual
+ *     rows, idx taken as 0), nothing of the old state is read, and the ring slots the clip does not reach are written
+ *     with the empty rows (n_b = 0 leaves exactly a re-initialised stream);
+ *   any other code (and code 2 with t0 > 0): advance from the state as it is; n_b = 0 leaves it untouched.
+ * t0 is the position of this call's first frame in the caller's clip: a clip longer than T runs as consecutive calls
+ * with t0 = 0, T, 2T, ..., x and out moved on by the caller, lengths and active unchanged.
+ * out rows t >= n_b are written as zeros.  Launches: 2 + 5 L whatever B and T are, grids sized from (B, T); a workgroup
+ * whose frame, row tile or ring slot lies beyond n_b returns after reading the code and the length.  push is the only
+ * launch that reads rings and writes none; state is the only launch that writes rings; taps and finish lie between.
+ * x: stream b's channel c of frame t at x[b * x_bstride + c * x_stride + t * V]; out: stream b's row t at
+ * out[b * out_bstride + t * K].  Scratch is stream-major; different layers' scratch may alias as in stgcn_co_clip.
+ * Limits are stgcn_co_clip's plus B >= 1; anything else, or a NULL required pointer (active and lengths included),
+ * returns 1 (2 for the dtype) before any launch; the two queries return -1. */
+typedef struct {
+  int Cin, Cout, P, Kt, S, res_mode, splits, pad_;
+  const float* A;       /* [P][V][V] graph * importance */
+  const float* wp;      /* packed gcn.conv weight, as in stgcn_co_clip_layer */
+  const float* bias2d;  /* [V][Cout] or NULL */
+  const float* wrp;     /* packed residual.0 weight (res_mode 2) */
+  const float* br;      /* [Cout] or NULL */
+  const float* ln1_w;   /* tcn.0, (C,1,V) as stored */
+  const float* ln1_b;
+  const float* ln2_w;   /* tcn.3 */
+  const float* ln2_b;
+  const float* lnr_w;   /* residual.1 (res_mode 2) */
+  const float* lnr_b;
+  const void* wt;       /* packed tcn.2 weight, dtype elements */
+  const float* bt;      /* [Cout] tcn.2 bias or NULL */
+  void* ring;           /* [B][fifo][V][Cout] dtype elements: the batch's state, as in stgcn_co_streams_layer */
+  float* res_ring;      /* [B][Kt/2+1][V][Cout] */
+  int* idx;             /* [B][2] */
+  float* z_buf;         /* [B][T][V][Cout] scratch */
+  float* r_buf;         /* [B][T][V][Cout] scratch (res_mode 2) */
+  void* hist;           /* [B][fifo-1 + T][V][Cout] scratch, dtype elements */
+  float* resq;          /* [B][Kt/2 + T][V][Cout] scratch */
+  float* partial;       /* [B][T][splits][V][Cout] scratch */
+  float* y;             /* [B][T][V][Cout] the layer's output rows */
+} stgcn_co_streams_clip_layer;
+typedef struct {
+  int B, T, t0, V, L, C0, K, dtype;
+  long x_stride;        /* elements between two channels of x */
+  long x_bstride;       /* elements between two streams of x */
+  long out_bstride;     /* elements between two streams of out */
+  const float* x;       /* this call's first frame of stream 0, see above */
+  const int* active;    /* [B] */
+  const int* lengths;   /* [B] */
+  const float* ln_w;    /* [3*V] */
+  const float* ln_b;
+  const float* w_in;    /* [C0][3] */
+  const float* b_in;    /* [C0] */
+  const float* w_out;   /* [K][C_last] */
+  const float* b_out;   /* [K] or NULL */
+  float* h0;            /* [B][T][V][C0] scratch: the first layer's input rows */
+  float* out;           /* stream b's [T][K] at out + b * out_bstride */
+  stgcn_co_streams_clip_layer layers[STGCN_RT_MAX_LAYERS];
+} stgcn_co_streams_clip_desc;
+int stgcn_co_streams_clip_splits(const stgcn_co_streams_clip_desc* d, int layer);
+long stgcn_co_streams_clip_workspace(const stgcn_co_streams_clip_desc* d, int layer);  /* bytes of layers[layer].partial */
+int stgcn_co_streams_clip(const stgcn_co_streams_clip_desc* d, void* stream);
 
 /* MS-TCN stage (models/mstcn/mstcn.py:68-116; ms_stage.hip): SingleStage = conv_in 1x1, num_layers
  * DilatedResidualLayers (dilation 2^i), conv_out 1x1, forward and backward, batch 1.  Activations are fp32 rows

@@ -387,6 +387,20 @@ int stgcn_co_clip(const stgcn_co_clip_desc* d, void* stream) {
   return rc != STGCN_OK ? rc : co_clip_launch(*d, STREAM(stream));
 }
 
+int stgcn_co_streams_clip_splits(const stgcn_co_streams_clip_desc* d, int layer) {
+  if (!d || co_streams_clip_check(*d, true) != STGCN_OK || layer < 0 || layer >= d->L) return -1;
+  return co_streams_clip_num_splits(*d, layer);
+}
+long stgcn_co_streams_clip_workspace(const stgcn_co_streams_clip_desc* d, int layer) {
+  const int n = stgcn_co_streams_clip_splits(d, layer);
+  return n < 1 ? -1 : (long)d->B * d->T * n * d->V * d->layers[layer].Cout * (long)sizeof(float);
+}
+int stgcn_co_streams_clip(const stgcn_co_streams_clip_desc* d, void* stream) {
+  if (!d) return STGCN_EBADSHAPE;
+  const int rc = co_streams_clip_check(*d, false);
+  return rc != STGCN_OK ? rc : co_streams_clip_launch(*d, STREAM(stream));
+}
+
 long stgcn_ms_pack_elems(int F) { return ms_pack_elems(F); }
 int stgcn_ms_pack_layer(const float* w1, const float* w2, int F, int kernel, void* dst, int dtype, void* stream) {
   return ms_pack_launch(w1, w2, F, kernel, dst, dtype, STREAM(stream));

@@ -1,0 +1,246 @@
+// CoST-GCN clip inference for a batch of B independent streams (stgcn_co_streams_clip): stream b advances by n_b
+// frames per call on the stream-major state of co_streams.hip.  Per stream this is co_clip.hip's clip: the stages are
+// clip_ops.h's, called on pointers offset to stream b, with n_b in the place of T and a restart flag.  active [B] and
+// lengths [B] are read on the device by every block (stream_frames), so a captured call replays with other codes and
+// lengths, and nothing is compacted on the host: a block whose frame, row tile or ring slot lies beyond n_b, or whose
+// stream has code 0, returns after those two loads (co_streams.hip's skip).
+//
+// Launches per call, 2 + 5 L whatever B and T are; blockIdx.x = b * (blocks per stream) + i:
+//   csc_in     : T blocks per stream: h0[b][t]                                                          (i < n_b)
+//   per layer:
+//   csc_gcn    : T per stream: z[b][t], r[b][t]                                                         (i < n_b)
+//   csc_push   : T + fifo-1 + Kt/2 per stream: frame i's push into hist[b] / resq[b] (i < n_b), then the carry blocks
+//                (n_b > 0): the stream's ring frames, or on a restart the empty FIFO's rows (ReLU(ln1_b) / zero) without
+//                a read of ring, res_ring or idx.  The ONLY launch that reads rings, and it writes none.
+//   csc_taps   : splits x ceil(T*V / 128) per stream: rows m = t*V + v < n_b*V, dense per stream; a row tile never spans
+//                two streams, whose histories are different buffers
+//   csc_finish : T per stream: y[b][t] (i < n_b); thread 0 of the stream's block 0 advances idx[b] by n_b, from 0 on a
+//                restart; no other thread of the launch reads idx
+//   csc_state  : fifo + Kt/2+1 per stream, one ring slot each: the min(n_b, slots) newest clip frames into the slots the
+//                per-frame route would have used; on a restart the other slots get the empty rows; otherwise the
+//                blocks beyond n_b return.  The ONLY launch that writes rings.
+//   csc_out    : T per stream: out[b][t], zero rows for t >= n_b and for skipped streams
+// Two kernel boundaries (taps, finish) lie between the last ring read and the first ring write, and nothing depends on
+// the order of blocks inside a launch: every block reads what earlier launches wrote and writes rows of its own.
+//
+// Order of every sum: clip_ops.h's, i.e. co_clip.hip's.  No atomics, no cooperative launch, no spin.  A stream's
+// outputs and state do not depend on B, its slot, T, t0 chunking or the other streams.
+#include "common.h"
+#include "launchers.h"
+#include "frame_ops.h"
+#include "clip_ops.h"
+#include "../../include/stgcn_amd.h"
+
+namespace {
+using namespace clip_ops;
+using layer_t = stgcn_co_streams_clip_layer;
+
+// what every block needs of the call besides its layer
+struct Call {
+  const int* active;
+  const int* lengths;
+  int T, t0;
+};
+
+// n_b = clamp(lengths[b] - t0, 0, T), or -1 for a skipped stream (no frame, carry or slot index is below it);
+// restart: code 2 on the first call of the caller's clip
+DEV int stream_frames(const Call c, long b, bool& restart) {
+  const int code = c.active[b], len = c.lengths[b];
+  restart = code == 2 && c.t0 == 0;
+  if (code == 0) return -1;
+  return len <= c.t0 ? 0 : min(len - c.t0, c.T);
+}
+
+// ---------------------------------------------------------------------------------------------------- heads
+__global__ __launch_bounds__(HNT) void csc_in_kernel(const Call c, const float* __restrict__ x, long x_stride,
+                                                     long x_bstride, int V, int C0, const float* __restrict__ ln_w,
+                                                     const float* __restrict__ ln_b, const float* __restrict__ w_in,
+                                                     const float* __restrict__ b_in, float* __restrict__ h0) {
+  __shared__ float xf[3 * VMAX];
+  __shared__ float xi[3 * VMAX];
+  __shared__ float red[HNT / 64];
+  const long b = blockIdx.x / c.T, t = blockIdx.x - b * c.T;
+  bool restart;
+  if (t >= stream_frames(c, b, restart)) return;
+  in_frame(x + b * x_bstride + t * V, x_stride, V, C0, ln_w, ln_b, w_in, b_in, xf, xi, red, h0 + (b * c.T + t) * V * C0);
+}
+
+__global__ __launch_bounds__(HNT) void csc_out_kernel(const Call c, const float* __restrict__ y, int V, int C,
+                                                      const float* __restrict__ w_out, const float* __restrict__ b_out,
+                                                      int K, float* __restrict__ out, long out_bstride) {
+  __shared__ float pool[CMAX];
+  const long b = blockIdx.x / c.T, t = blockIdx.x - b * c.T;
+  float* o = out + b * out_bstride + t * K;
+  bool restart;
+  if (t >= stream_frames(c, b, restart)) {
+    for (int k = threadIdx.x; k < K; k += HNT) o[k] = 0.f;
+    return;
+  }
+  frame_head_out<HNT>(y + (b * c.T + t) * V * C, C, V, C, w_out, b_out, K, pool, o);
+}
+
+// ---------------------------------------------------------------------------------------------------- per layer
+// x: the layer's input rows [B][T][V][Cin]
+__global__ __launch_bounds__(GNT) void csc_gcn_kernel(const layer_t ly, const Call c, int V, const float* __restrict__ x) {
+  __shared__ __attribute__((aligned(16))) float xs[VMAX * (CMAX + XPAD)];
+  const long b = blockIdx.x / c.T, t = blockIdx.x - b * c.T, E = (long)V * ly.Cout, f = b * c.T + t;
+  bool restart;
+  if (t >= stream_frames(c, b, restart)) return;
+  gcn_frame(ly, V, x + f * V * ly.Cin, ly.z_buf + f * E, ly.r_buf + f * E, xs);
+}
+
+template <typename T>
+__global__ __launch_bounds__(FNT) void csc_push_kernel(const layer_t ly, const Call c, int V, const float* __restrict__ x) {
+  __shared__ float red[FNT / 64];
+  const long E = (long)V * ly.Cout;
+  const int fifo = ring_slots(ly.S, ly.Kt), R = res_slots(ly.Kt), per = c.T + fifo - 1 + R - 1;
+  const long b = blockIdx.x / per;
+  const int i = (int)(blockIdx.x - b * per);
+  bool restart;
+  const int n = stream_frames(c, b, restart);
+  T* hist = reinterpret_cast<T*>(ly.hist) + b * (fifo - 1 + c.T) * E;
+  float* resq = ly.resq + b * (R - 1 + c.T) * E;
+  if (i < c.T) {
+    if (i >= n) return;
+    const long f = b * c.T + i;
+    const float* res = ly.res_mode == 2 ? ly.r_buf + f * E : x + f * E;  // mode 1: Cin == Cout
+    push_frame<T>(ly, V, i, ly.z_buf + f * E, res, hist, resq, red);
+    return;
+  }
+  if (n <= 0) return;  // no frame of this call reads the stream's history
+  carry_block<T>(ly, V, i - c.T, restart, reinterpret_cast<const T*>(ly.ring) + b * fifo * E, ly.res_ring + b * R * E,
+                 ly.idx + b * 2, hist, resq);
+}
+
+template <typename T, int TU>
+__global__ __launch_bounds__(TNT) void csc_taps_kernel(const layer_t ly, const Call c, int V, int nks, int nsplit,
+                                                       int ngroup) {
+  __shared__ float red[TNW][16][64];
+  const int per = nsplit * ngroup;
+  const long b = blockIdx.x / per;
+  const int i = (int)(blockIdx.x - b * per), grp = i / nsplit, s = i - grp * nsplit, m0 = grp * (G * 32);
+  bool restart;
+  const int M = stream_frames(c, b, restart) * V;
+  if (m0 >= M) return;  // uniform over the block
+  const long E = (long)V * ly.Cout;
+  const int Hh = ring_slots(ly.S, ly.Kt) - 1;
+  taps_block<T, TU>(ly, V, M, nks, nsplit, s, m0, reinterpret_cast<const T*>(ly.hist) + b * (Hh + c.T) * E,
+                    ly.partial + b * c.T * nsplit * E, red);
+}
+
+__global__ __launch_bounds__(FNT) void csc_finish_kernel(const layer_t ly, const Call c, int V, int nsplit) {
+  __shared__ float red[FNT / 64];
+  const long b = blockIdx.x / c.T, t = blockIdx.x - b * c.T, E = (long)V * ly.Cout, f = b * c.T + t;
+  bool restart;
+  const int n = stream_frames(c, b, restart);
+  if (t < n)
+    finish_frame(ly, V, nsplit, ly.partial + f * nsplit * E, ly.resq + (b * (res_slots(ly.Kt) - 1 + c.T) + t) * E,
+                 ly.y + f * E, red);
+  if (t == 0 && threadIdx.x == 0 && (n > 0 || (n == 0 && restart)))  // code 1 with no frame: idx stays as it is
+    advance_idx(ly.idx + b * 2, ly.S, ly.Kt, n, restart);
+}
+
+template <typename T>
+__global__ __launch_bounds__(FNT) void csc_state_kernel(const layer_t ly, const Call c, int V) {
+  const long E = (long)V * ly.Cout;
+  const int fifo = ring_slots(ly.S, ly.Kt), R = res_slots(ly.Kt), per = fifo + R;
+  const long b = blockIdx.x / per;
+  const int i = (int)(blockIdx.x - b * per);
+  const bool res = i >= fifo;
+  const int j = res ? i - fifo : i;
+  bool restart;
+  const int n = stream_frames(c, b, restart);
+  if (n < 0 || (j >= n && !restart)) return;
+  state_block<T>(ly, V, n, res, j, restart, reinterpret_cast<T*>(ly.ring) + b * fifo * E, ly.res_ring + b * R * E,
+                 ly.idx + b * 2, reinterpret_cast<const T*>(ly.hist) + b * (fifo - 1 + c.T) * E,
+                 ly.resq + b * (R - 1 + c.T) * E);
+}
+
+// the single-frame descriptor that carries the same shape: co_check's limits are this route's limits
+stgcn_co_layer as_co_layer(const stgcn_co_streams_clip_desc& d, const layer_t& y) {
+  stgcn_co_layer c = {};
+  c.V = d.V, c.Cin = y.Cin, c.Cout = y.Cout, c.P = y.P, c.Kt = y.Kt, c.S = y.S;
+  c.res_mode = y.res_mode, c.dtype = d.dtype, c.splits = y.splits;
+  return c;
+}
+
+// the largest grid of a call, per stream: a layer's push, state or tap blocks (shapes already checked)
+long max_blocks_per_stream(const stgcn_co_streams_clip_desc& d) {
+  const long groups = ((long)d.T * d.V + G * 32 - 1) / (G * 32);
+  long n = d.T;
+  for (int l = 0; l < d.L; ++l) {
+    const layer_t& y = d.layers[l];
+    const long slots = ring_slots(y.S, y.Kt) + res_slots(y.Kt);
+    n = std::max(n, std::max(d.T + slots, num_splits(y.Cout, y.Kt, y.splits) * groups));
+  }
+  return n;
+}
+
+template <typename T>
+void launch_layer(const layer_t& y, const Call& c, int B, int V, int nsplit, const float* x, hipStream_t s) {
+  const unsigned fifo = ring_slots(y.S, y.Kt), R = res_slots(y.Kt), Tn = c.T, nb = B;
+  const int nks = num_ksteps(y.Cout, y.Kt), ngroup = (c.T * V + G * 32 - 1) / (G * 32);
+  hipLaunchKernelGGL(csc_gcn_kernel, dim3(nb * Tn), dim3(GNT), 0, s, y, c, V, x);
+  hipLaunchKernelGGL(csc_push_kernel<T>, dim3(nb * (Tn + fifo - 1 + R - 1)), dim3(FNT), 0, s, y, c, V, x);
+  constexpr int TU = sizeof(T) == 2 ? 4 : 2;
+  hipLaunchKernelGGL((csc_taps_kernel<T, TU>), dim3(nb * nsplit * ngroup), dim3(TNT), 0, s, y, c, V, nks, nsplit, ngroup);
+  hipLaunchKernelGGL(csc_finish_kernel, dim3(nb * Tn), dim3(FNT), 0, s, y, c, V, nsplit);
+  hipLaunchKernelGGL(csc_state_kernel<T>, dim3(nb * (fifo + R)), dim3(FNT), 0, s, y, c, V);
+}
+
+}  // namespace
+
+// 0 when the descriptor's shapes, dtype and (unless shapes_only) pointers are usable
+int co_streams_clip_check(const stgcn_co_streams_clip_desc& d, bool shapes_only) {
+  if (d.B < 1 || d.T < 1 || d.T > STGCN_CO_CLIP_MAX_T || d.t0 < 0 || d.L < 1 || d.L > STGCN_RT_MAX_LAYERS || d.K < 1 ||
+      d.C0 < 4 || d.C0 > CMAX || d.C0 % 4)
+    return STGCN_EBADSHAPE;
+  int cin = d.C0;
+  for (int l = 0; l < d.L; ++l) {
+    const layer_t& y = d.layers[l];
+    if (y.Cin != cin) return STGCN_EBADSHAPE;
+    const int rc = co_check(as_co_layer(d, y), true);  // shapes first, then the dtype
+    if (rc != STGCN_OK) return rc;
+    cin = y.Cout;
+  }
+  if ((long)d.B * max_blocks_per_stream(d) > 0x7fffffffL) return STGCN_EBADSHAPE;  // blockIdx.x carries (stream, block)
+  if (shapes_only) return STGCN_OK;
+  if (!d.x || d.x_stride < (long)d.T * d.V || !d.active || !d.lengths || !d.ln_w || !d.ln_b || !d.w_in || !d.b_in ||
+      !d.w_out || !d.h0 || !d.out || d.out_bstride < (long)d.T * d.K)
+    return STGCN_EBADSHAPE;
+  if (d.B > 1 && d.x_bstride < 3 * d.x_stride) return STGCN_EBADSHAPE;
+  for (int l = 0; l < d.L; ++l) {
+    const layer_t& y = d.layers[l];
+    if (!y.A || !y.wp || !y.ln1_w || !y.ln1_b || !y.ln2_w || !y.ln2_b || !y.wt || !y.ring || !y.res_ring || !y.idx ||
+        !y.z_buf || !y.hist || !y.resq || !y.partial || !y.y ||
+        (y.res_mode == 2 && (!y.wrp || !y.lnr_w || !y.lnr_b || !y.r_buf)))
+      return STGCN_EBADSHAPE;
+  }
+  return STGCN_OK;
+}
+
+// K splits of layer l's tap stage: co_clip_num_splits' rule, a function of (Cout, Kt) and the forced count alone
+int co_streams_clip_num_splits(const stgcn_co_streams_clip_desc& d, int l) {
+  const layer_t& y = d.layers[l];
+  return num_splits(y.Cout, y.Kt, y.splits);
+}
+
+int co_streams_clip_launch(const stgcn_co_streams_clip_desc& d, hipStream_t s) {
+  const int B = d.B, V = d.V;
+  const Call c = {d.active, d.lengths, d.T, d.t0};
+  const unsigned nbt = (unsigned)B * (unsigned)d.T;
+  hipLaunchKernelGGL(csc_in_kernel, dim3(nbt), dim3(HNT), 0, s, c, d.x, d.x_stride, d.x_bstride, V, d.C0, d.ln_w, d.ln_b,
+                     d.w_in, d.b_in, d.h0);
+  const float* x = d.h0;
+  for (int l = 0; l < d.L; ++l) {
+    const layer_t& y = d.layers[l];
+    const int nsplit = co_streams_clip_num_splits(d, l);
+    if (d.dtype == 0) launch_layer<float>(y, c, B, V, nsplit, x, s);
+    else launch_layer<bf16>(y, c, B, V, nsplit, x, s);
+    x = y.y;
+  }
+  const layer_t& last = d.layers[d.L - 1];
+  hipLaunchKernelGGL(csc_out_kernel, dim3(nbt), dim3(HNT), 0, s, c, x, V, last.Cout, d.w_out, d.b_out, d.K, d.out,
+                     d.out_bstride);
+  return hipGetLastError() == hipSuccess ? STGCN_OK : STGCN_EHIP;
+}

@@ -12,9 +12,10 @@
 //   co_finish_stage<NTH>           co_finish_kernel (1024, stream 0), cs_finish_kernel (1024, stream b)
 //   ring_unit / load_ring<T>       cs_taps_kernel<T, TU>; co_taps_kernel<T> keeps its load_a<T>(ring, ...)
 //   ln_stats_units<NTH, U>         rt_streams_kernel (512), the push / finish stages (1024)
-// co_clip.hip (frame t of a clip in the place of stream b) instantiates the heads, conv_tile_acc / amix_*,
-// co_push_stage and ring_unit like co_streams.hip; cc_finish_kernel restates co_finish_stage's arithmetic with the
-// residual row taken from the clip's linear buffer (no ring head to read or store).
+// The clip routes (co_clip.hip, co_streams_clip.hip: frame t of a clip in the place of stream b) go through
+// clip_ops.h, which instantiates the heads, conv_tile_acc / amix_*, co_push_stage and ring_unit like co_streams.hip;
+// its finish_frame restates co_finish_stage's arithmetic with the residual row taken from the clip's linear buffer (no
+// ring head to read or store).
 //
 // rt_frame_kernel (the one-launch persistent kernel of rt_fused.hip) keeps its own bodies: its sums go through DPP
 // reductions in another fixed order.  It shares the constants below only.  The dot8 graph conv of rt_gcn_kernel and

@@ -1114,6 +1114,30 @@ def co_clip(desc, x, t0, T, out):
     L.check(L.lib().stgcn_co_clip(ctypes.byref(desc), L.stream()), "co_clip")
 
 
+def co_streams_clip_workspace(desc, layer):
+    """(K-split count, bytes of the split partials) of layer ``layer`` of a stgcn_co_streams_clip_desc (shapes, B and T
+    filled in); raises on shapes the kernels do not take."""
+    n = L.lib().stgcn_co_streams_clip_splits(ctypes.byref(desc), layer)
+    nbytes = L.lib().stgcn_co_streams_clip_workspace(ctypes.byref(desc), layer)
+    if n < 1 or nbytes < 0:
+        raise RuntimeError("stgcn_amd: co-st-gcn stream batch clip shape not supported (B >= 1, V <= 32, P <= 3, "
+                           f"C % 4 == 0, C <= 256, odd Kt <= 69, stride 1 or 2, at most {L.RT_MAX_LAYERS} layers, "
+                           f"1 <= T <= {L.CO_CLIP_MAX_T})")
+    return n, nbytes
+
+
+def co_streams_clip(desc, x, t0, T, active, lengths, out):
+    """Frames t0 .. t0+T-1 of the clips x (B, 3, T_all, V) fp32 dense through a CoST-GCN stream batch
+    (stgcn_co_streams_clip): stream b takes those below lengths[b]; rows t0 .. t0+T-1 of out (B, T_all, K).  active,
+    lengths (B) int32 on the device; ``desc`` is the batch's stgcn_co_streams_clip_desc (costgcn.CoStreamBatch)."""
+    T_all, V = x.shape[2], x.shape[3]
+    desc.T, desc.t0 = T, t0
+    desc.x_stride, desc.x_bstride, desc.out_bstride = T_all * V, 3 * T_all * V, T_all * out.shape[2]
+    desc.x, desc.out = x.data_ptr() + 4 * t0 * V, out.data_ptr() + 4 * t0 * out.shape[2]
+    desc.active, desc.lengths = active.data_ptr(), lengths.data_ptr()
+    L.check(L.lib().stgcn_co_streams_clip(ctypes.byref(desc), L.stream()), "co_streams_clip")
+
+
 # ------------------------------------------------------------------------------ MS-TCN stage (ms_stage.hip)
 MS_MODES = {"logits": 0, "logsoftmax": 1, "softmax": 2}  # the `refine` / `output_type` selectors
 

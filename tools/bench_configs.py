@@ -30,6 +30,10 @@ co_clip:  co-st-gcn clip inference (Model.forward_clip, stgcn_co_clip) at Kt in 
           16, 64, 256}: device ms per captured clip and per frame, rings filled, beside the per-frame route
           graph-replayed in the same run in alternating windows; rows appended to profiles/co_clip.jsonl.  Only with
           --only co_clip.
+co_streams_clip: co-st-gcn stream-batch clips (CoStreamBatch.step_clip, stgcn_co_streams_clip) at Kt in {9, 69} x
+          {fp32, bf16} x B in {1, 8, 64} x T in {4, 16, 64}: device ms of one captured step_clip, rings filled, beside
+          B replays of a captured forward_clip of T frames and T replays of a captured step of B streams in the same run
+          in alternating windows; rows appended to profiles/co_streams_clip.jsonl.  Only with --only co_streams_clip.
 streams:  config 3 as a stream batch (Model.stream_batch, stgcn_rt_streams): B in {1, 8, 64, 256, 1024} streams
           advanced one frame per launch, HIP-event device time over 200 graph-replayed ticks after the FIFOs have
           filled, beside the single-stream one-launch route (stgcn_rt_frame) graph-replayed in the same run: ms per
@@ -37,7 +41,7 @@ streams:  config 3 as a stream batch (Model.stream_batch, stgcn_rt_streams): B i
           bf16) are measured in the same process, interleaved per B, --stream-repeats times over; the rows are also
           appended to profiles/rt_streams.jsonl.  Only with --only streams.
 
-    python tools/bench_configs.py [--frames 2000] [--steps 10] [--only 3|5|ln|f1|co|ms|streams|co_streams|co_clip]
+    python tools/bench_configs.py [--frames 2000] [--steps 10] [--only 3|5|ln|f1|co|ms|streams|co_streams|co_clip|co_streams_clip]
 Prints one JSON line per config.
 """
 import argparse
@@ -535,6 +539,69 @@ def co_clip(P, dev, kernel, dtype, Ts=(1, 4, 16, 64, 256), repeats=3):
     return rows
 
 
+def co_streams_clip(P, dev, kernel, dtype, batches=(1, 8, 64), Ts=(4, 16, 64), repeats=3):
+    """Rows of the co-st-gcn stream-batch clip table: the reference schedule at temporal kernel ``kernel`` in
+    ``dtype``, one step_clip of B streams x T frames (one stgcn_co_streams_clip call: clip_frames raised to B * T)
+    captured as a HIP graph, beside (a) B replays of a captured forward_clip of T frames and (b) T replays of a captured
+    step of B streams, in the same run with the rings filled.  The timed windows alternate ``repeats`` times; each row
+    gives the median and the min / max of its windows."""
+    arch = {"strategy": "spatial", "in_feat": 3, "stages": 1, "kernel": kernel, "output_type": "logits",
+            "normalization": "LayerNorm", "num_classes": 52, "graph": P.PKU_MMD,
+            "st-gcn": dict(LAYERS, kernel=kernel, latency=False, importance=True, in_feat=3, stages=1,
+                           dilation=[1] * 9)}
+    torch.manual_seed(0)
+    m = P.MODELS["co-st-gcn"](rank=None, **arch).to(dev).eval().set_compute_dtype(dtype)
+    fill = max(arch["st-gcn"]["stride"]) * (kernel - 1) + 1
+    gen = torch.Generator(device=dev).manual_seed(3)
+    med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
+    rows = []
+    with torch.no_grad():
+        xc = {T: torch.randn(1, 3, T, 25, device=dev, generator=gen) for T in Ts}
+        single = {T: _capture(lambda T=T: m.forward_clip(xc[T])) for T in Ts}
+        for _ in range(-(-fill // min(Ts))):
+            single[min(Ts)].replay()
+        for B in batches:
+            sb = m.stream_batch(B)
+            sb.clip_frames = max(sb.clip_frames, B * max(Ts))
+            x1 = torch.randn(B, 3, 1, 25, device=dev, generator=gen)
+            tick = _capture(lambda: sb.step(x1))
+            for _ in range(fill):
+                tick.replay()
+            for T in Ts:
+                x = torch.randn(B, 3, T, 25, device=dev, generator=gen)
+                clip = _capture(lambda: sb.step_clip(x))
+                # every window at least ~256 frames of one stream and at least 3 replays
+                reps = max(3, 256 // (B * T))
+                t_clip, t_a, t_b = [], [], []
+                for _ in range(repeats):
+                    t_clip.append(_timed(clip, reps))
+                    t_a.append(_timed(single[T], reps * B) * B)
+                    t_b.append(_timed(tick, reps * T) * T)
+                ms, a, b = med(t_clip), med(t_a), med(t_b)
+                rows.append({"config": "co-st-gcn stream-batch clip (stgcn_co_streams_clip), ln/costgcn_local.json "
+                                       f"widths, Kt={kernel}: one step_clip of B streams x T frames",
+                             "dtype": dtype, "Kt": kernel, "B": B, "T": T, "step_clip_device_ms": round(ms, 4),
+                             "step_clip_ms_min_max": [round(min(t_clip), 4), round(max(t_clip), 4)],
+                             "B_forward_clips_device_ms": round(a, 4),
+                             "B_forward_clips_ms_min_max": [round(min(t_a), 4), round(max(t_a), 4)],
+                             "T_step_ticks_device_ms": round(b, 4),
+                             "T_step_ticks_ms_min_max": [round(min(t_b), 4), round(max(t_b), 4)],
+                             "ratio_B_forward_clips_over_step_clip": round(a / ms, 2),
+                             "ratio_T_step_ticks_over_step_clip": round(b / ms, 2),
+                             "frames_per_s": round(B * T / ms * 1e3, 1),
+                             "k_splits": [sb._desc()[0].layers[i].splits for i in range(9)],
+                             "launches_per_step_clip": 2 + 5 * 9, "clip_frames": sb.clip_frames,
+                             "clip_scratch_bytes": sb.scratch_bytes - sb._step_bytes,
+                             "state_bytes_per_stream": sb.state_bytes // B,
+                             "note": f"HIP events around graph replays ({reps} step_clips, {reps * B} forward_clips, "
+                                     f"{reps * T} ticks per window), {repeats} alternating windows, rings filled; no "
+                                     "per-kernel trace"})
+                del clip
+            del sb, tick
+            torch.cuda.empty_cache()
+    return rows
+
+
 MS_TCN = {"latency": False, "importance": True, "stages": 3, "layers": [10, 10, 10], "kernel": [3, 3, 3],
           "filters": [64, 64, 64], "dropout": [0, 0, 0]}
 MSGCN_ARCH = {"strategy": "spatial", "receptive_field": 50, "segment": 2000, "in_feat": 3, "stages": 4,
@@ -687,6 +754,13 @@ def main():
             for kernel in (9, 69):
                 for dtype in ("fp32", "bf16"):
                     for row in co_clip(P, dev, kernel, dtype):
+                        print(json.dumps(row), flush=True)
+                        f.write(json.dumps(row) + "\n")
+    if args.only == "co_streams_clip":
+        with open(os.path.join(ROOT, "profiles", "co_streams_clip.jsonl"), "a") as f:
+            for kernel in (9, 69):
+                for dtype in ("fp32", "bf16"):
+                    for row in co_streams_clip(P, dev, kernel, dtype):
                         print(json.dumps(row), flush=True)
                         f.write(json.dumps(row) + "\n")
     if args.only == "co":
