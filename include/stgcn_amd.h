@@ -40,7 +40,8 @@ extern "C" {
  *      conv operands), stgcn_rt_streams_layer.wp / wrp became const void* of that element type, and
  *      stgcn_rt_streams_pack_weight_as was added — no size, offset or existing entry point changed;
  *      still 7: stgcn_co_clip* added (co_clip.hip) — additive likewise;
- *      still 7: stgcn_co_streams_clip* added (co_streams_clip.hip) — additive likewise. */
+ *      still 7: stgcn_co_streams_clip* added (co_streams_clip.hip) — additive likewise;
+ *      still 7: stgcn_rt_streams_clip* added (rt_streams_clip.hip) — additive likewise. */
 #define STGCN_ABI_VERSION 7
 
 /* Implicit-GEMM (Kt x 1) row convolution; see conv_rows.hip for the exact contract.
@@ -809,6 +810,57 @@ typedef struct {
 int stgcn_co_streams_clip_splits(const stgcn_co_streams_clip_desc* d, int layer);
 long stgcn_co_streams_clip_workspace(const stgcn_co_streams_clip_desc* d, int layer);  /* bytes of layers[layer].partial */
 int stgcn_co_streams_clip(const stgcn_co_streams_clip_desc* d, void* stream);
+
+/* RT-ST-GCN clip inference for B independent streams (rt_streams_clip.hip): one call advances stream b by n_b frames
+ * on the stream-major state of stgcn_rt_streams (fifo [B][fifo_size][V][Cout], acc [B][S][V][Cout], idx [B][2]: the
+ * same buffers, so per-frame ticks and clips mix on one batch).  layers[] are stgcn_rt_streams_layer as that call takes
+ * them (the same packed weight images of desc.dtype, the same [V][Cout] norm rows).
+ * active [B] and lengths [B] are device int32, read by the kernels (a captured call replays with other values):
+ *   n_b = clamp(lengths[b] - t0, 0, T) frames are consumed, frames 0 .. n_b-1 of this call's T;
+ *   code 0: skip — state untouched and unread, every out row of the stream zero;
+ *   code 2 and t0 == 0: restart, then advance — fifo, acc and idx are taken as zero, nothing of the old state is read,
+ *     and the slots the clip does not reach are cleared (n_b = 0 leaves exactly a reset stream);
+ *   any other code (and code 2 with t0 > 0): advance from the state as it is; n_b = 0 leaves it untouched.
+ * t0 is the position of this call's first frame in the caller's clip: a clip longer than T runs as consecutive calls
+ * with t0 = 0, T, 2T, ..., x and out moved on by the caller, lengths and active unchanged.
+ * Per frame the arithmetic is stgcn_rt_streams's (the conv, A-mix, bias2d, LayerNorm, residual and head stages are the
+ * same device functions with the same block size); the FIFO step a = acc[ai] + z - fifo[fi]; acc[ai] = a; fifo[fi] = z
+ * runs in exactly this association frame after frame, one thread per 4 elements of a stream for the whole call.  The
+ * order of every sum depends on the network only: a stream's out, fifo, acc and idx are bit-identical whatever B, its
+ * slot, T, t0 chunking and the other streams' codes, lengths and contents are.
+ * Launches: 2 L + 1 whatever B and T are (frame kernel 0: input head + layer 0's conv; scan of layer l; frame kernel
+ * l + 1: layer l's norms and residual + layer l+1's conv, the last one the output head), grids sized from (B, T); a
+ * workgroup whose stream is skipped or whose frame lies beyond n_b returns after reading the code and the length.
+ * out rows t >= n_b are written as zeros.  x: stream b's channel c of frame t at x[b * x_bstride + c * x_stride + t * V];
+ * out: stream b's row t at out[b * out_bstride + t * K].  Scratch: xb, z, r, a, each [B][T][fstride] floats with
+ * fstride >= the largest V * C of the network (C0 included) and fstride % 4 == 0; shared by all layers.
+ * Limits are stgcn_rt_streams's, plus 1 <= T <= STGCN_RT_CLIP_MAX_T, t0 >= 0 and B * T < 2^31.  A NULL required pointer
+ * (active and lengths included; r only with a res_mode 2 layer) or a shape outside the limits returns 1 (2 for the
+ * dtype) before any launch. */
+#define STGCN_RT_CLIP_MAX_T 256
+typedef struct {
+  int B, T, t0, V, L, C0, K, dtype;
+  long x_stride;        /* elements between two channels of x */
+  long x_bstride;       /* elements between two streams of x */
+  long out_bstride;     /* elements between two streams of out */
+  long fstride;         /* elements between two frames of the scratch buffers */
+  const float* x;       /* this call's first frame of stream 0, see above */
+  const int* active;    /* [B] */
+  const int* lengths;   /* [B] */
+  const float* ln_w;    /* [3*V] */
+  const float* ln_b;
+  const float* w_in;    /* [C0][3] */
+  const float* b_in;    /* [C0] */
+  const float* w_out;   /* [K][C_last] */
+  const float* b_out;   /* [K] or NULL */
+  float* xb;            /* [B][T][fstride] scratch: the current layer's input rows [V][C] */
+  float* z;             /* [B][T][fstride] scratch: bias2d + the A-mixed conv */
+  float* r;             /* [B][T][fstride] scratch: the residual conv (res_mode 2 layers), or NULL */
+  float* a;             /* [B][T][fstride] scratch: the running box sum per frame */
+  float* out;           /* stream b's [T][K] at out + b * out_bstride */
+  stgcn_rt_streams_layer layers[STGCN_RT_MAX_LAYERS];
+} stgcn_rt_streams_clip_desc;
+int stgcn_rt_streams_clip(const stgcn_rt_streams_clip_desc* d, void* stream);
 
 /* MS-TCN stage (models/mstcn/mstcn.py:68-116; ms_stage.hip): SingleStage = conv_in 1x1, num_layers
  * DilatedResidualLayers (dilation 2^i), conv_out 1x1, forward and backward, batch 1.  Activations are fp32 rows

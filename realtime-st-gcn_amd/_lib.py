@@ -163,6 +163,17 @@ class CoStreamsClipDesc(ctypes.Structure):  # stgcn_co_streams_clip_desc
                [("layers", CoStreamsClipLayer * RT_MAX_LAYERS)]
 
 
+RT_CLIP_MAX_T = 256  # STGCN_RT_CLIP_MAX_T
+
+
+class RtStreamsClipDesc(ctypes.Structure):  # stgcn_rt_streams_clip_desc
+    _fields_ = [(n, c_int) for n in ("B", "T", "t0", "V", "L", "C0", "K", "dtype")] + \
+               [(n, c_long) for n in ("x_stride", "x_bstride", "out_bstride", "fstride")] + \
+               [(n, c_void_p) for n in ("x", "active", "lengths", "ln_w", "ln_b", "w_in", "b_in", "w_out", "b_out",
+                                        "xb", "z", "r", "a", "out")] + \
+               [("layers", RtStreamsLayer * RT_MAX_LAYERS)]
+
+
 class MsLayer(ctypes.Structure):  # stgcn_ms_layer
     _fields_ = [(n, c_int) for n in ("R", "V", "F", "dil", "dtype", "pad_")] + \
                [(n, c_void_p) for n in ("x", "wp", "b1", "b2", "y", "h", "dy", "g", "dx", "part", "grads")]
@@ -274,6 +285,7 @@ _SIGS = {
     "stgcn_co_streams_clip_splits": (c_int, [ctypes.POINTER(CoStreamsClipDesc), c_int]),
     "stgcn_co_streams_clip_workspace": (c_long, [ctypes.POINTER(CoStreamsClipDesc), c_int]),
     "stgcn_co_streams_clip": (c_int, [ctypes.POINTER(CoStreamsClipDesc), c_void_p]),
+    "stgcn_rt_streams_clip": (c_int, [ctypes.POINTER(RtStreamsClipDesc), c_void_p]),
     "stgcn_ms_pack_elems": (c_long, [c_int]),
     "stgcn_ms_pack_layer": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
     "stgcn_ms_wgrad_blocks": (c_int, [c_int]),

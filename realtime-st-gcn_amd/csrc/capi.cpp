@@ -400,6 +400,9 @@ int stgcn_co_streams_clip(const stgcn_co_streams_clip_desc* d, void* stream) {
   const int rc = co_streams_clip_check(*d, false);
   return rc != STGCN_OK ? rc : co_streams_clip_launch(*d, STREAM(stream));
 }
+int stgcn_rt_streams_clip(const stgcn_rt_streams_clip_desc* d, void* stream) {
+  return d ? rt_streams_clip_launch(*d, STREAM(stream)) : STGCN_EBADSHAPE;
+}
 
 long stgcn_ms_pack_elems(int F) { return ms_pack_elems(F); }
 int stgcn_ms_pack_layer(const float* w1, const float* w2, int F, int kernel, void* dst, int dtype, void* stream) {

@@ -140,6 +140,8 @@ int co_clip_launch(const stgcn_co_clip_desc& d, hipStream_t s);
 int co_streams_clip_check(const stgcn_co_streams_clip_desc& d, bool shapes_only);
 int co_streams_clip_num_splits(const stgcn_co_streams_clip_desc& d, int layer);
 int co_streams_clip_launch(const stgcn_co_streams_clip_desc& d, hipStream_t s);
+// rt_streams_clip.hip
+int rt_streams_clip_launch(const stgcn_rt_streams_clip_desc& d, hipStream_t s);
 // ms_stage.hip
 long ms_pack_elems(int F);
 int ms_pack_launch(const float* w1, const float* w2, int F, int kernel, void* dst, int dtype, hipStream_t s);

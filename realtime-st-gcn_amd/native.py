@@ -1138,6 +1138,18 @@ def co_streams_clip(desc, x, t0, T, active, lengths, out):
     L.check(L.lib().stgcn_co_streams_clip(ctypes.byref(desc), L.stream()), "co_streams_clip")
 
 
+def rt_streams_clip(desc, x, t0, T, active, lengths, out):
+    """Frames t0 .. t0+T-1 of the clips x (B, 3, T_all, V) fp32 dense through an rt-st-gcn stream batch
+    (stgcn_rt_streams_clip): stream b takes those below lengths[b]; rows t0 .. t0+T-1 of out (B, T_all, K).  active,
+    lengths (B) int32 on the device; ``desc`` is the batch's stgcn_rt_streams_clip_desc (rtstgcn.RtStreamBatch)."""
+    T_all, V = x.shape[2], x.shape[3]
+    desc.T, desc.t0 = T, t0
+    desc.x_stride, desc.x_bstride, desc.out_bstride = T_all * V, 3 * T_all * V, T_all * out.shape[2]
+    desc.x, desc.out = x.data_ptr() + 4 * t0 * V, out.data_ptr() + 4 * t0 * out.shape[2]
+    desc.active, desc.lengths = active.data_ptr(), lengths.data_ptr()
+    L.check(L.lib().stgcn_rt_streams_clip(ctypes.byref(desc), L.stream()), "rt_streams_clip")
+
+
 # ------------------------------------------------------------------------------ MS-TCN stage (ms_stage.hip)
 MS_MODES = {"logits": 0, "logsoftmax": 1, "softmax": 2}  # the `refine` / `output_type` selectors
 

@@ -34,6 +34,10 @@ co_streams_clip: co-st-gcn stream-batch clips (CoStreamBatch.step_clip, stgcn_co
           {fp32, bf16} x B in {1, 8, 64} x T in {4, 16, 64}: device ms of one captured step_clip, rings filled, beside
           B replays of a captured forward_clip of T frames and T replays of a captured step of B streams in the same run
           in alternating windows; rows appended to profiles/co_streams_clip.jsonl.  Only with --only co_streams_clip.
+rt_streams_clip: config 3 as stream-batch clips (RtStreamBatch.step_clip, stgcn_rt_streams_clip): B in {1, 8, 64, 256}
+          x T in {4, 16, 64}, fp32 and bf16, one captured step_clip beside T replays of a captured step of the same
+          batch, in alternating windows; rows appended to profiles/rt_streams_clip.jsonl.  Only with
+          --only rt_streams_clip.
 streams:  config 3 as a stream batch (Model.stream_batch, stgcn_rt_streams): B in {1, 8, 64, 256, 1024} streams
           advanced one frame per launch, HIP-event device time over 200 graph-replayed ticks after the FIFOs have
           filled, beside the single-stream one-launch route (stgcn_rt_frame) graph-replayed in the same run: ms per
@@ -41,7 +45,7 @@ streams:  config 3 as a stream batch (Model.stream_batch, stgcn_rt_streams): B i
           bf16) are measured in the same process, interleaved per B, --stream-repeats times over; the rows are also
           appended to profiles/rt_streams.jsonl.  Only with --only streams.
 
-    python tools/bench_configs.py [--frames 2000] [--steps 10] [--only 3|5|ln|f1|co|ms|streams|co_streams|co_clip|co_streams_clip]
+    python tools/bench_configs.py [--frames 2000] [--steps 10] [--only 3|5|ln|f1|co|ms|streams|co_streams|co_clip|co_streams_clip|rt_streams_clip]
 Prints one JSON line per config.
 """
 import argparse
@@ -602,6 +606,57 @@ def co_streams_clip(P, dev, kernel, dtype, batches=(1, 8, 64), Ts=(4, 16, 64), r
     return rows
 
 
+def rt_streams_clip(P, dev, batches=(1, 8, 64, 256), Ts=(4, 16, 64), repeats=3):
+    """Rows of the rt-st-gcn stream-batch clip table: config 3's widths and strides, V = 25, per operand type one
+    step_clip of B streams x T frames (one stgcn_rt_streams_clip call: clip_frames raised to B * T) captured as a HIP
+    graph, beside T replays of a captured step of B streams in the same run and process, rings filled.  The timed
+    windows alternate ``repeats`` times; each row gives the median and the min / max of its windows."""
+    torch.manual_seed(0)
+    m = P.MODELS["rt-st-gcn"](rank=None, **dict(RT_ARCH, graph=P.PKU_MMD)).to(dev)
+    m.eval()
+    m.prepare_benchmark(RT_ARCH)
+    gen = torch.Generator(device=dev).manual_seed(3)
+    fill = 32  # > the 17-frame FIFO of the stride-2 layers
+    med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
+    rows = []
+    with torch.no_grad():
+        for B in batches:
+            for dtype in ("fp32", "bf16"):
+                sb = m.stream_batch(B, dtype)
+                sb.clip_frames = max(sb.clip_frames, B * max(Ts))
+                x1 = torch.randn(B, 3, 1, 25, device=dev, generator=gen)
+                tick = _capture(lambda: sb.step(x1))
+                for _ in range(fill):
+                    tick.replay()
+                for T in Ts:
+                    x = torch.randn(B, 3, T, 25, device=dev, generator=gen)
+                    clip = _capture(lambda: sb.step_clip(x))
+                    reps = max(3, 256 // (B * T))  # every window at least ~256 frames of one stream and 3 replays
+                    t_clip, t_tick = [], []
+                    for _ in range(repeats):
+                        t_clip.append(_timed(clip, reps))
+                        t_tick.append(_timed(tick, reps * T) * T)
+                    ms, b = med(t_clip), med(t_tick)
+                    rows.append({"config": "3 as a stream-batch clip (stgcn_rt_streams_clip): one step_clip of B streams "
+                                           "x T frames", "dtype": dtype, "B": B, "T": T,
+                                 "step_clip_device_ms": round(ms, 4),
+                                 "step_clip_ms_min_max": [round(min(t_clip), 4), round(max(t_clip), 4)],
+                                 "T_step_ticks_device_ms": round(b, 4),
+                                 "T_step_ticks_ms_min_max": [round(min(t_tick), 4), round(max(t_tick), 4)],
+                                 "ratio_T_step_ticks_over_step_clip": round(b / ms, 2),
+                                 "ratio_min_max": [round(min(t_tick) / max(t_clip), 2),
+                                                   round(max(t_tick) / min(t_clip), 2)],
+                                 "frames_per_s": round(B * T / ms * 1e3, 1), "launches_per_step_clip": 2 * 9 + 1,
+                                 "clip_frames": sb.clip_frames, "clip_scratch_bytes": sb.scratch_bytes,
+                                 "state_bytes_per_stream": sb.state_bytes // B,
+                                 "note": f"HIP events around graph replays ({reps} step_clips, {reps * T} ticks per "
+                                         f"window), {repeats} alternating windows, rings filled; no per-kernel trace"})
+                    del clip
+                del sb, tick
+                torch.cuda.empty_cache()
+    return rows
+
+
 MS_TCN = {"latency": False, "importance": True, "stages": 3, "layers": [10, 10, 10], "kernel": [3, 3, 3],
           "filters": [64, 64, 64], "dropout": [0, 0, 0]}
 MSGCN_ARCH = {"strategy": "spatial", "receptive_field": 50, "segment": 2000, "in_feat": 3, "stages": 4,
@@ -763,6 +818,11 @@ def main():
                     for row in co_streams_clip(P, dev, kernel, dtype):
                         print(json.dumps(row), flush=True)
                         f.write(json.dumps(row) + "\n")
+    if args.only == "rt_streams_clip":
+        with open(os.path.join(ROOT, "profiles", "rt_streams_clip.jsonl"), "a") as f:
+            for row in rt_streams_clip(P, dev):
+                print(json.dumps(row), flush=True)
+                f.write(json.dumps(row) + "\n")
     if args.only == "co":
         for kernel in (9, 69):
             for dtype in ("fp32", "bf16"):
