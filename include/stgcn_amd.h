@@ -41,7 +41,8 @@ extern "C" {
  *      stgcn_rt_streams_pack_weight_as was added — no size, offset or existing entry point changed;
  *      still 7: stgcn_co_clip* added (co_clip.hip) — additive likewise;
  *      still 7: stgcn_co_streams_clip* added (co_streams_clip.hip) — additive likewise;
- *      still 7: stgcn_rt_streams_clip* added (rt_streams_clip.hip) — additive likewise. */
+ *      still 7: stgcn_rt_streams_clip* added (rt_streams_clip.hip) — additive likewise;
+ *      still 7: stgcn_stream_state* added (stream_state.hip) — additive likewise. */
 #define STGCN_ABI_VERSION 7
 
 /* Implicit-GEMM (Kt x 1) row convolution; see conv_rows.hip for the exact contract.
@@ -861,6 +862,47 @@ typedef struct {
   stgcn_rt_streams_layer layers[STGCN_RT_MAX_LAYERS];
 } stgcn_rt_streams_clip_desc;
 int stgcn_rt_streams_clip(const stgcn_rt_streams_clip_desc* d, void* stream);
+
+/* Snapshot and restore of live streams of the stream batches (stream_state.hip; additive to ABI 7): the per-layer state
+ * of stgcn_rt_streams (kind 0: s0 = fifo [B][n0 = fifo_size][V][C], s1 = acc [B][n1 = S][V][C]) or of stgcn_co_streams
+ * (kind 1: s0 = ring [B][n0 = S*(Kt-1)+1][V][C] in dtype elements, s1 = res_ring [B][n1 = Kt/2+1][V][C]) and idx [B][2],
+ * to and from the canonical image.  A snapshot is snap [n][E] fp32: row i is stream slots[i], layer-major, and each
+ * state tensor t of a layer is stored rotated along its slot axis so that it is the original with stored index 0:
+ *   snap[i][off_t + k * V*C + e] = tensor_t[slots[i]][(idx[slots[i]][t] + k) % n_t][e],   k < n_t, e < V*C.
+ * Every per-frame and clip kernel addresses a slot only relative to the stored index, so a stream continued from its
+ * canonical image with idx = (0, 0) returns the same bits.  No value is recomputed (the rt accumulators are copied).
+ * The element type of s0 is bf16 for kind 1 with dtype 1 and fp32 otherwise (the rt-st-gcn state is fp32 in both of its
+ * dtypes); a bf16 value is widened exactly on export and an image value is rounded to nearest even on import.
+ *   stgcn_stream_state_export: snap[i] = the canonical image of stream slots[i]; state and idx are not written.
+ *   stgcn_stream_state_import: stream slots[i] = snap[i] at rotation 0, idx[slots[i]] = (0, 0); other streams are not
+ *                              touched.  Two entries of slots naming one stream make that stream's content undefined.
+ * One launch each for all layers and all n streams, 256 threads per workgroup, 16-byte accesses on the [V][C] rows, no
+ * atomics, no barrier between workgroups, no host synchronisation: slots (device int32 [n]) and idx are read by the
+ * kernel, so a captured call replays with other slots.  An entry of slots outside [0, B) is skipped: its workgroups
+ * return without touching memory (its export row stays as it was).
+ * The image is dense: layers[0].off0 = 0, off1 = off0 + n0*V*C, the next layer's off0 = off1 + n1*V*C, E = the end.
+ * Limits: 1 <= L <= STGCN_RT_MAX_LAYERS, 2 <= V <= 32, C >= 4 and C % 4 == 0, n0, n1 >= 1, B >= 1, n >= 1, kind 0 | 1;
+ * an offset or E that disagrees with the above, or a NULL pointer, returns 1 and a dtype other than 0 | 1 returns 2,
+ * before any launch. */
+#define STGCN_STREAM_STATE_RT 0
+#define STGCN_STREAM_STATE_CO 1
+typedef struct {
+  void* s0;             /* fifo (kind 0, fp32) | ring (kind 1, dtype elements): [B][n0][V][C] */
+  float* s1;            /* acc (kind 0) | res_ring (kind 1): [B][n1][V][C] */
+  int* idx;             /* [B][2] */
+  int C, n0, n1, pad_;
+  long off0, off1;      /* first element of s0's / s1's part in a snapshot row */
+} stgcn_stream_state_layer;
+typedef struct {
+  int kind, V, L, B, n, dtype;
+  const int* slots;     /* [n] device: the streams, in snapshot row order */
+  float* snap;          /* [n][E] device */
+  long E;               /* elements per snapshot row */
+  stgcn_stream_state_layer layers[STGCN_RT_MAX_LAYERS];
+} stgcn_stream_state_desc;
+int stgcn_stream_state_check(const stgcn_stream_state_desc* d);  /* the code either call would return, no launch */
+int stgcn_stream_state_export(const stgcn_stream_state_desc* d, void* stream);
+int stgcn_stream_state_import(const stgcn_stream_state_desc* d, void* stream);
 
 /* MS-TCN stage (models/mstcn/mstcn.py:68-116; ms_stage.hip): SingleStage = conv_in 1x1, num_layers
  * DilatedResidualLayers (dilation 2^i), conv_out 1x1, forward and backward, batch 1.  Activations are fp32 rows

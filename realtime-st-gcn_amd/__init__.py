@@ -9,6 +9,7 @@ from .syncbn import convert_sync_batchnorm, revert_sync_batchnorm  # noqa: F401
 from .graph import Graph, PKU_MMD  # noqa: F401
 from .modules import BatchNorm1d, ConvTemporalGraphical, LayerNorm, StgcnLayer, set_compute_dtype  # noqa: F401
 from .stgcn import Model as Stgcn  # noqa: F401
+from .streams import StreamSnapshot  # noqa: F401
 
 MODELS = {
     "st-gcn": Stgcn,

@@ -174,6 +174,20 @@ class RtStreamsClipDesc(ctypes.Structure):  # stgcn_rt_streams_clip_desc
                [("layers", RtStreamsLayer * RT_MAX_LAYERS)]
 
 
+STREAM_STATE_RT, STREAM_STATE_CO = 0, 1  # STGCN_STREAM_STATE_RT / _CO
+
+
+class StreamStateLayer(ctypes.Structure):  # stgcn_stream_state_layer
+    _fields_ = [(n, c_void_p) for n in ("s0", "s1", "idx")] + [(n, c_int) for n in ("C", "n0", "n1", "pad_")] + \
+               [("off0", c_long), ("off1", c_long)]
+
+
+class StreamStateDesc(ctypes.Structure):  # stgcn_stream_state_desc
+    _fields_ = [(n, c_int) for n in ("kind", "V", "L", "B", "n", "dtype")] + [("slots", c_void_p), ("snap", c_void_p),
+                                                                             ("E", c_long)] + \
+               [("layers", StreamStateLayer * RT_MAX_LAYERS)]
+
+
 class MsLayer(ctypes.Structure):  # stgcn_ms_layer
     _fields_ = [(n, c_int) for n in ("R", "V", "F", "dil", "dtype", "pad_")] + \
                [(n, c_void_p) for n in ("x", "wp", "b1", "b2", "y", "h", "dy", "g", "dx", "part", "grads")]
@@ -286,6 +300,9 @@ _SIGS = {
     "stgcn_co_streams_clip_workspace": (c_long, [ctypes.POINTER(CoStreamsClipDesc), c_int]),
     "stgcn_co_streams_clip": (c_int, [ctypes.POINTER(CoStreamsClipDesc), c_void_p]),
     "stgcn_rt_streams_clip": (c_int, [ctypes.POINTER(RtStreamsClipDesc), c_void_p]),
+    "stgcn_stream_state_check": (c_int, [ctypes.POINTER(StreamStateDesc)]),
+    "stgcn_stream_state_export": (c_int, [ctypes.POINTER(StreamStateDesc), c_void_p]),
+    "stgcn_stream_state_import": (c_int, [ctypes.POINTER(StreamStateDesc), c_void_p]),
     "stgcn_ms_pack_elems": (c_long, [c_int]),
     "stgcn_ms_pack_layer": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
     "stgcn_ms_wgrad_blocks": (c_int, [c_int]),

@@ -36,7 +36,7 @@ from . import layer_fn as LF
 from . import native as K
 from .graph import Graph
 from .modules import ConvTemporalGraphical, LayerNorm, resolve_dtype
-from .streams import Keep, StreamBatch, f32, fill_heads, res_mode_of
+from .streams import Keep, StreamBatch, export_streams, f32, fill_heads, import_streams, res_mode_of
 
 
 class CoStgcnLayer(nn.Module):
@@ -314,6 +314,24 @@ class Model(nn.Module):
                     K.co_clip(self._clip_desc(plan, n), x, t0, n, out)
         return out.t().unsqueeze(0)
 
+    def _own_state(self):
+        plan, _ = self._ensure()  # a rebuild restarts the stream: it has to come first
+        return [(ring, res_ring, idx) for _, ring, res_ring, idx in plan["state"]]
+
+    def export_state(self):
+        """The model's own stream (the one ``forward`` / ``forward_clip`` advance) as a one-row StreamSnapshot: the
+        plan's rings and indices have a stream batch's per-stream layout, so stgcn_stream_state_export runs on them with
+        B = 1, and the snapshot imports into a slot of ``stream_batch(B)`` (and back).  Only meaningful for the
+        parameters it was taken under."""
+        return export_streams("co", 1, self.compute_dtype, self._own_state(), None, "Model.export_state")
+
+    def import_state(self, snap):
+        """A one-row StreamSnapshot into the model's own stream (cast to the ring's dtype).  The buffers keep their
+        addresses, so a captured graph of a frame or a clip stays valid."""
+        if getattr(snap, "n", 1) != 1:
+            raise RuntimeError(f"stgcn_amd: Model.import_state takes a snapshot of one stream, got {snap.n}")
+        import_streams("co", 1, self.compute_dtype, self._own_state(), snap, None, None, "Model.import_state")
+
     def stream_batch(self, B, splits=0):
         """B independent skeleton streams of this model, advanced together one frame per call (CoStreamBatch,
         stgcn_co_streams).  ``splits`` forces the tap stage's K-split count of every layer (0: the library's choice, a
@@ -336,6 +354,8 @@ class CoStreamBatch(StreamBatch):
     was allocated) and survive a rebuild of the weight packs and the descriptor, which follows ``Model._key()``.  An
     empty FIFO is ReLU(tcn.0.bias), so a parameter change makes the stream state stale: a rebuild restarts every
     stream, as it does for the single-stream model."""
+
+    kind = "co"
 
     def __init__(self, model, B, splits=0):
         super().__init__(model, B)

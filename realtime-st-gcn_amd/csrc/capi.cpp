@@ -403,6 +403,15 @@ int stgcn_co_streams_clip(const stgcn_co_streams_clip_desc* d, void* stream) {
 int stgcn_rt_streams_clip(const stgcn_rt_streams_clip_desc* d, void* stream) {
   return d ? rt_streams_clip_launch(*d, STREAM(stream)) : STGCN_EBADSHAPE;
 }
+int stgcn_stream_state_check(const stgcn_stream_state_desc* d) { return d ? stream_state_check(*d) : STGCN_EBADSHAPE; }
+int stgcn_stream_state_export(const stgcn_stream_state_desc* d, void* stream) {
+  const int rc = stgcn_stream_state_check(d);
+  return rc != STGCN_OK ? rc : stream_state_export_launch(*d, STREAM(stream));
+}
+int stgcn_stream_state_import(const stgcn_stream_state_desc* d, void* stream) {
+  const int rc = stgcn_stream_state_check(d);
+  return rc != STGCN_OK ? rc : stream_state_import_launch(*d, STREAM(stream));
+}
 
 long stgcn_ms_pack_elems(int F) { return ms_pack_elems(F); }
 int stgcn_ms_pack_layer(const float* w1, const float* w2, int F, int kernel, void* dst, int dtype, void* stream) {

@@ -142,6 +142,10 @@ int co_streams_clip_num_splits(const stgcn_co_streams_clip_desc& d, int layer);
 int co_streams_clip_launch(const stgcn_co_streams_clip_desc& d, hipStream_t s);
 // rt_streams_clip.hip
 int rt_streams_clip_launch(const stgcn_rt_streams_clip_desc& d, hipStream_t s);
+// stream_state.hip
+int stream_state_check(const stgcn_stream_state_desc& d);
+int stream_state_export_launch(const stgcn_stream_state_desc& d, hipStream_t s);
+int stream_state_import_launch(const stgcn_stream_state_desc& d, hipStream_t s);
 // ms_stage.hip
 long ms_pack_elems(int F);
 int ms_pack_launch(const float* w1, const float* w2, int F, int kernel, void* dst, int dtype, hipStream_t s);

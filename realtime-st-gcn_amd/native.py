@@ -1150,6 +1150,17 @@ def rt_streams_clip(desc, x, t0, T, active, lengths, out):
     L.check(L.lib().stgcn_rt_streams_clip(ctypes.byref(desc), L.stream()), "rt_streams_clip")
 
 
+def stream_state_export(desc):
+    """The canonical images of streams ``desc.slots`` into ``desc.snap`` in one launch (stgcn_stream_state_export);
+    ``desc`` is a stgcn_stream_state_desc (streams.state_desc)."""
+    L.check(L.lib().stgcn_stream_state_export(ctypes.byref(desc), L.stream()), "stream_state_export")
+
+
+def stream_state_import(desc):
+    """Rows of ``desc.snap`` into streams ``desc.slots`` at rotation 0 in one launch (stgcn_stream_state_import)."""
+    L.check(L.lib().stgcn_stream_state_import(ctypes.byref(desc), L.stream()), "stream_state_import")
+
+
 # ------------------------------------------------------------------------------ MS-TCN stage (ms_stage.hip)
 MS_MODES = {"logits": 0, "logsoftmax": 1, "softmax": 2}  # the `refine` / `output_type` selectors
 

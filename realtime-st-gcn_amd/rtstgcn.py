@@ -26,7 +26,7 @@ from .syncbn import active_sync
 from .graph import Graph
 from .modules import BatchNorm1d, LayerNorm, make_norm, resolve_dtype
 from .stgcn import IN_PAD
-from .streams import Keep, StreamBatch, f32, fill_heads, ln_rows, res_mode_of
+from .streams import Keep, StreamBatch, export_streams, f32, fill_heads, import_streams, ln_rows, res_mode_of
 
 
 class OfflineLayer(nn.Module):
@@ -373,6 +373,26 @@ class Model(nn.Module):
             if isinstance(layer, OnlineLayer):
                 layer.aggregate.reset()
 
+    def _own_state(self, what):
+        if not self.online or not all(isinstance(l, OnlineLayer) for l in self.st_gcn):
+            raise RuntimeError(f"stgcn_amd: {what} needs the online layers: call prepare_benchmark first")
+        return [(l.aggregate.fifo, l.aggregate.accumulator, l.aggregate.idx) for l in self.st_gcn]
+
+    def export_state(self):
+        """The model's own stream (the one ``forward`` advances, online form) as a one-row StreamSnapshot: the layers'
+        FIFO, accumulators and indices have a stream batch's per-stream layout, so stgcn_stream_state_export runs on them
+        with B = 1, and the snapshot imports into a slot of ``stream_batch(B)`` (and back)."""
+        return export_streams("rt", 1, torch.float32, self._own_state("Model.export_state"), None,
+                              "Model.export_state")
+
+    def import_state(self, snap):
+        """A one-row StreamSnapshot into the model's own stream.  The state buffers keep their addresses (only their
+        contents change, as with reset_state), so the one-launch frame descriptor stays valid."""
+        state = self._own_state("Model.import_state")
+        if getattr(snap, "n", 1) != 1:
+            raise RuntimeError(f"stgcn_amd: Model.import_state takes a snapshot of one stream, got {snap.n}")
+        import_streams("rt", 1, torch.float32, state, snap, None, None, "Model.import_state")
+
     def prepare_benchmark(self, arch_conf):
         """Intended semantics of rtstgcn.py:190-197 (which calls a missing method): swap to online layers
         and fold the edge importance (OnlineLayer.eval_)."""
@@ -392,6 +412,11 @@ class RtStreamBatch(StreamBatch):
 
     The state buffers live here and survive a rebuild of the descriptor (which follows the parameters' data
     pointers and in-place versions, as Model._frame_key does); the model's own single-stream state is not used."""
+
+    kind = "rt"
+
+    def _state_dtype(self):
+        return self.dtype  # the conv operands' type; the state itself is fp32 in both
 
     def __init__(self, model, B, dtype=None):
         try:

@@ -1,5 +1,6 @@
 """What the per-frame (continual inference) routes share on the host: the stream-batch surface of
-``rtstgcn.RtStreamBatch`` and ``costgcn.CoStreamBatch``, and the helpers their descriptor builders fill with."""
+``rtstgcn.RtStreamBatch`` and ``costgcn.CoStreamBatch``, the helpers their descriptor builders fill with, and the
+snapshot of live streams (``StreamSnapshot``, stgcn_stream_state_export / _import)."""
 from __future__ import annotations
 
 import torch
@@ -40,6 +41,216 @@ def fill_heads(d, model, keep):
     d.b_out = keep(f32(model.fcn_out.bias))
 
 
+# ---------------------------------------------------------------------------------------------- stream snapshots
+KINDS = ("rt", "co")  # STGCN_STREAM_STATE_RT, STGCN_STREAM_STATE_CO
+LAYOUT_FIELDS = ("C", "n0", "n1", "off0", "off1")
+
+
+def state_layout(V, shapes):
+    """The layout table of a stream's canonical image: per layer (C, n0, n1, off0, off1) from ``shapes`` = per layer
+    (C, n0, n1), n0 / n1 the slot counts of the layer's two state tensors (rt: fifo, acc; co: ring, res_ring), each
+    stored [slots][V][C], layer-major and dense.  Returns (table, E = elements per stream)."""
+    at, table = 0, []
+    for C, n0, n1 in shapes:
+        C, n0, n1 = int(C), int(n0), int(n1)
+        table.append((C, n0, n1, at, at + n0 * V * C))
+        at += (n0 + n1) * V * C
+    return tuple(table), at
+
+
+def layout_of_state(state):
+    """(V, layout table, E) of per-layer state tensors (t0 [B or none][n0][V][C], t1 [...][n1][V][C], idx)."""
+    V = state[0][0].shape[-2]
+    table, E = state_layout(V, [(t0.shape[-1], t0.shape[-3], t1.shape[-3]) for t0, t1, _ in state])
+    return V, table, E
+
+
+class StreamSnapshot:
+    """The state of ``n`` streams taken out of a stream batch or a single-stream model: ``data`` [n][E] fp32, one
+    canonical image per stream (every layer's two state tensors rotated so that both stored indices are 0; fp32
+    whatever the batch's dtype), ``kind`` ("rt" | "co"), ``V`` and ``layout``: per layer (C, n0, n1, off0, off1), the
+    slot counts of the layer's two tensors and their offsets in a row.
+
+    Weights are not part of a snapshot: it is only meaningful for the parameters it was taken under (a co-st-gcn ring
+    caches ReLU(LN1(z)), an rt-st-gcn accumulator sums graph-conv outputs).  Rows can be selected (``snap[i]``,
+    ``snap[[i, j]]``), joined (``StreamSnapshot.cat``), moved (``to``) and saved (``state_dict`` / ``from_state_dict``
+    through ``torch.save`` / ``torch.load``)."""
+
+    def __init__(self, kind, V, layout, data):
+        if kind not in KINDS:
+            raise RuntimeError(f"stgcn_amd: StreamSnapshot kind must be one of {KINDS}, got {kind!r}")
+        layout = tuple(tuple(int(v) for v in row) for row in layout)
+        if not layout or any(len(row) != len(LAYOUT_FIELDS) for row in layout):
+            raise RuntimeError("stgcn_amd: StreamSnapshot layout needs one (C, n0, n1, off0, off1) row per layer")
+        want, E = state_layout(int(V), [row[:3] for row in layout])
+        if want != layout:
+            raise RuntimeError("stgcn_amd: StreamSnapshot layout offsets are not the dense layer-major ones")
+        if not torch.is_tensor(data) or data.dim() != 2 or data.shape[1] != E or data.dtype != torch.float32:
+            raise RuntimeError(f"stgcn_amd: StreamSnapshot data must be fp32 of shape (n, {E}), got "
+                               f"{tuple(data.shape) if torch.is_tensor(data) else type(data).__name__}")
+        self.kind, self.V, self.layout, self.E, self.data = kind, int(V), layout, E, data.contiguous()
+
+    @property
+    def n(self):
+        return self.data.shape[0]
+
+    def __len__(self):
+        return self.n
+
+    @property
+    def device(self):
+        return self.data.device
+
+    def to(self, device):
+        return StreamSnapshot(self.kind, self.V, self.layout, self.data.to(device))
+
+    def __getitem__(self, rows):
+        if isinstance(rows, int):
+            rows = [rows]
+        rows = torch.as_tensor(list(rows), dtype=torch.long)
+        if rows.numel() and (int(rows.min()) < -self.n or int(rows.max()) >= self.n):
+            raise IndexError(f"stgcn_amd: StreamSnapshot row out of range for {self.n} streams")
+        return StreamSnapshot(self.kind, self.V, self.layout, self.data[rows.to(self.data.device)])
+
+    @staticmethod
+    def cat(snaps):
+        snaps = list(snaps)
+        if not snaps:
+            raise RuntimeError("stgcn_amd: StreamSnapshot.cat needs at least one snapshot")
+        for s in snaps[1:]:
+            why = layout_mismatch((snaps[0].kind, snaps[0].V, snaps[0].layout), (s.kind, s.V, s.layout))
+            if why:
+                raise RuntimeError(f"stgcn_amd: StreamSnapshot.cat: snapshots differ: {why}")
+        return StreamSnapshot(snaps[0].kind, snaps[0].V, snaps[0].layout, torch.cat([s.data for s in snaps], dim=0))
+
+    def state_dict(self):
+        """Plain tensors and ints: ``torch.save`` / ``torch.load`` round-trips it."""
+        return {"version": 1, "kind": KINDS.index(self.kind), "V": self.V, "E": self.E,
+                "layout": torch.tensor(self.layout, dtype=torch.int64), "data": self.data}
+
+    @staticmethod
+    def from_state_dict(d):
+        if d.get("version") != 1:
+            raise RuntimeError(f"stgcn_amd: unknown StreamSnapshot version {d.get('version')!r}")
+        if d["kind"] not in (0, 1):
+            raise RuntimeError(f"stgcn_amd: unknown StreamSnapshot kind code {d['kind']!r}")
+        snap = StreamSnapshot(KINDS[d["kind"]], d["V"], d["layout"].tolist(), d["data"])
+        if snap.E != d["E"]:
+            raise RuntimeError(f"stgcn_amd: StreamSnapshot state_dict names E = {d['E']}, its layout gives {snap.E}")
+        return snap
+
+
+def layout_mismatch(have, want):
+    """None when (kind, V, layout) ``have`` equals ``want``, else a sentence naming the first differing field."""
+    if have[0] != want[0]:
+        return f"kind {have[0]!r} != {want[0]!r}"
+    if len(have[2]) != len(want[2]):
+        return f"layer count {len(have[2])} != {len(want[2])}"
+    if have[1] != want[1]:
+        return f"V {have[1]} != {want[1]}"
+    names = {"rt": ("C", "fifo slots (n0)", "accumulator slots (n1 = stride)", "off0", "off1"),
+             "co": ("C", "ring slots (n0 = S*(Kt-1)+1)", "residual ring slots (n1 = Kt/2+1)", "off0", "off1")}[have[0]]
+    for l, (a, b) in enumerate(zip(have[2], want[2])):
+        for name, u, v in zip(names, a, b):
+            if u != v:
+                return f"layer {l}: {name} {u} != {v}"
+    return None
+
+
+def check_slots(streams, B, what, unique):
+    """A Python sequence of slots, checked on the host: every slot in [0, B), and no slot twice when ``unique``."""
+    slots = [int(s) for s in streams]
+    for s in slots:
+        if not 0 <= s < B:
+            raise RuntimeError(f"stgcn_amd: {what}: slot {s} outside [0, {B})")
+    if unique and len(set(slots)) != len(slots):
+        dup = next(s for i, s in enumerate(slots) if s in slots[:i])
+        raise RuntimeError(f"stgcn_amd: {what}: slot {dup} is targeted twice")
+    return slots
+
+
+def is_device_slots(t):
+    return torch.is_tensor(t) and t.dtype == torch.int32 and t.is_cuda
+
+
+def state_desc(kind, V, B, dtype, state, layout, E, slots, data):
+    """The stgcn_stream_state_desc of per-layer state tensors (t0, t1, idx) with a leading stream axis of B (or none
+    when B == 1), ``slots`` int32 [n] and ``data`` fp32 [n][E], both on the state's device."""
+    d = K.L.StreamStateDesc()
+    d.kind, d.V, d.L, d.B, d.n, d.dtype = KINDS.index(kind), V, len(state), B, slots.shape[0], K.L.dtype_code(dtype)
+    d.slots, d.snap, d.E = slots.data_ptr(), data.data_ptr(), E
+    for y, (t0, t1, idx), row in zip(d.layers, state, layout):
+        y.s0, y.s1, y.idx = t0.data_ptr(), t1.data_ptr(), idx.data_ptr()
+        y.C, y.n0, y.n1, y.off0, y.off1 = row
+    return d
+
+
+def export_streams(kind, B, dtype, state, streams, what):
+    """``StreamBatch.export_state`` on any per-layer state (a batch's, or a single-stream model's with B = 1)."""
+    V, layout, E = layout_of_state(state)
+    dev = state[0][0].device
+    K.L.require_device(state[0][0])
+    with K.device_of(state[0][0]):
+        if streams is None:
+            slots = torch.arange(B, dtype=torch.int32, device=dev)
+        elif is_device_slots(streams):
+            slots = streams.contiguous()
+        else:
+            slots = torch.tensor(check_slots(streams, B, what, False), dtype=torch.int32, device=dev)
+        if slots.dim() != 1 or slots.shape[0] < 1:
+            raise RuntimeError(f"stgcn_amd: {what}: streams must name at least one slot in one dimension")
+        # a device slot tensor may hold entries the kernel skips: their rows stay zero
+        data = (torch.zeros if is_device_slots(streams) else torch.empty)((slots.shape[0], E), dtype=torch.float32,
+                                                                         device=dev)
+        K.stream_state_export(state_desc(kind, V, B, dtype, state, layout, E, slots, data))
+    return StreamSnapshot(kind, V, layout, data)
+
+
+def check_import(kind, B, state, snap, streams, select, what):
+    """The host refusals of ``import_state``, before anything touches a device -> (rows of snap or None, slots)."""
+    if not isinstance(snap, StreamSnapshot):
+        raise RuntimeError(f"stgcn_amd: {what} expects a StreamSnapshot, got {type(snap).__name__}")
+    V, layout, _ = layout_of_state(state)
+    why = layout_mismatch((snap.kind, snap.V, snap.layout), (kind, V, layout))
+    if why:
+        raise RuntimeError(f"stgcn_amd: {what}: the snapshot does not fit this model: {why}")
+    rows = None
+    if select is not None:
+        rows = [int(r) for r in ([select] if isinstance(select, int) else select)]
+        for r in rows:
+            if not 0 <= r < snap.n:
+                raise RuntimeError(f"stgcn_amd: {what}: select row {r} outside [0, {snap.n})")
+    n = snap.n if rows is None else len(rows)
+    if n < 1:
+        raise RuntimeError(f"stgcn_amd: {what}: nothing to import (no rows)")
+    if streams is None:
+        streams = list(range(n))
+    if is_device_slots(streams):
+        if streams.dim() != 1 or streams.shape[0] != n:
+            raise RuntimeError(f"stgcn_amd: {what}: {n} rows for streams of shape {tuple(streams.shape)}")
+        return rows, streams.contiguous()
+    slots = check_slots(streams, B, what, True)
+    if len(slots) != n:
+        raise RuntimeError(f"stgcn_amd: {what}: {n} rows for {len(slots)} slots")
+    return rows, slots
+
+
+def import_streams(kind, B, dtype, state, snap, streams, select, what):
+    """``StreamBatch.import_state`` on any per-layer state (a batch's, or a single-stream model's with B = 1)."""
+    rows, slots = check_import(kind, B, state, snap, streams, select, what)
+    K.L.require_device(state[0][0])
+    dev = state[0][0].device
+    if snap.device != dev:
+        raise RuntimeError(f"stgcn_amd: {what}: the snapshot lives on {snap.device}, the state on {dev}: move it with "
+                           "snapshot.to(device)")
+    with K.device_of(state[0][0]):
+        data = snap.data if rows is None else snap.data[torch.tensor(rows, dtype=torch.long, device=dev)]
+        if not torch.is_tensor(slots):
+            slots = torch.tensor(slots, dtype=torch.int32, device=dev)
+        V, layout, E = layout_of_state(state)
+        K.stream_state_import(state_desc(kind, V, B, dtype, state, layout, E, slots, data))
+
+
 class StreamBatch:
     """B independent skeleton streams of one per-frame model.  A subclass keeps ``state`` (per layer, a tuple of
     stream-major device tensors), builds its descriptor in ``_desc()`` -> (descriptor, keep-alive list) and launches
@@ -60,6 +271,36 @@ class StreamBatch:
     @property
     def state_bytes(self):
         return sum(t.numel() * t.element_size() for ts in self.state for t in ts)
+
+    # ------------------------------------------------------------------ snapshots: streams out of and into slots
+    kind = None  # "rt" | "co": the subclass's state family (stgcn_stream_state_desc.kind)
+
+    def _state_dtype(self):
+        """The batch's compute dtype as stgcn_stream_state_desc.dtype takes it."""
+        return self.state[0][0].dtype
+
+    def export_state(self, streams=None):
+        """The state of the given slots as a ``StreamSnapshot`` on the batch's device, in one launch
+        (stgcn_stream_state_export): ``streams`` None (all B, in slot order), a Python list of slots, or an int32 device
+        tensor used as given with no host sync (an entry outside [0, B) leaves its row zero).  The batch is not changed.
+        The snapshot is only meaningful for the parameters it was taken under."""
+        name = f"{type(self).__name__}.export_state"
+        if streams is not None and not is_device_slots(streams):
+            streams = check_slots(streams, self.B, name, False)
+        self._desc()
+        return export_streams(self.kind, self.B, self._state_dtype(), self.state, streams, name)
+
+    def import_state(self, snap, streams=None, select=None):
+        """Rows ``select`` of ``snap`` (default: all) into slots ``streams`` (default: 0 .. n-1), in one launch
+        (stgcn_stream_state_import); other slots are untouched.  ``streams``: a Python list (checked on the host: in
+        range, no slot twice) or an int32 device tensor used as given with no host sync (an entry outside [0, B) is
+        skipped; a slot named twice ends with undefined content).  A snapshot whose kind or layout table differs from
+        this batch's model is refused.  Values are cast to the state's dtype (a bf16 ring rounds to nearest even; fp32
+        is exact), and the stream continues bit for bit as the exported one would have under the same parameters."""
+        name = f"{type(self).__name__}.import_state"
+        check_import(self.kind, self.B, self.state, snap, streams, select, name)
+        self._desc()  # a rebuild restarts every stream (co-st-gcn): it has to come first
+        import_streams(self.kind, self.B, self._state_dtype(), self.state, snap, streams, select, name)
 
     def step(self, x, active=None):
         """x (B, 3, 1, V) -> (B, num_classes, 1).  ``active``: None (every stream steps), an int32 device tensor

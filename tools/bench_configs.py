@@ -38,6 +38,11 @@ rt_streams_clip: config 3 as stream-batch clips (RtStreamBatch.step_clip, stgcn_
           x T in {4, 16, 64}, fp32 and bf16, one captured step_clip beside T replays of a captured step of the same
           batch, in alternating windows; rows appended to profiles/rt_streams_clip.jsonl.  Only with
           --only rt_streams_clip.
+stream_state: snapshots of live co-st-gcn streams (CoStreamBatch.export_state / import_state, stgcn_stream_state_*) at
+          Kt in {9, 69} x {fp32, bf16}, B = 64, all 64 streams: HIP-event device ms of the captured export and import,
+          beside a captured torch.clone of the snapshot's bytes (the machine's copy rate at this size) and the
+          torch-level composition (per stream and layer roll + copy_, the heads read back to the host) in the same run; rows
+          appended to profiles/stream_state.jsonl.  Only with --only stream_state.
 streams:  config 3 as a stream batch (Model.stream_batch, stgcn_rt_streams): B in {1, 8, 64, 256, 1024} streams
           advanced one frame per launch, HIP-event device time over 200 graph-replayed ticks after the FIFOs have
           filled, beside the single-stream one-launch route (stgcn_rt_frame) graph-replayed in the same run: ms per
@@ -45,7 +50,7 @@ streams:  config 3 as a stream batch (Model.stream_batch, stgcn_rt_streams): B i
           bf16) are measured in the same process, interleaved per B, --stream-repeats times over; the rows are also
           appended to profiles/rt_streams.jsonl.  Only with --only streams.
 
-    python tools/bench_configs.py [--frames 2000] [--steps 10] [--only 3|5|ln|f1|co|ms|streams|co_streams|co_clip|co_streams_clip|rt_streams_clip]
+    python tools/bench_configs.py [--frames 2000] [--steps 10] [--only 3|5|ln|f1|co|ms|streams|co_streams|co_clip|co_streams_clip|rt_streams_clip|stream_state]
 Prints one JSON line per config.
 """
 import argparse
@@ -657,6 +662,67 @@ def rt_streams_clip(P, dev, batches=(1, 8, 64, 256), Ts=(4, 16, 64), repeats=3):
     return rows
 
 
+def stream_state(P, dev, kernel, dtype, B=64, reps=20):
+    """One row of the snapshot table: the reference schedule at temporal kernel ``kernel`` in ``dtype`` as a batch of B
+    streams out of step, every stream exported and imported in one launch each, beside torch.clone of the same number
+    of bytes and the torch-level composition of the same copy."""
+    arch = {"strategy": "spatial", "in_feat": 3, "stages": 1, "kernel": kernel, "output_type": "logits",
+            "normalization": "LayerNorm", "num_classes": 52, "graph": P.PKU_MMD,
+            "st-gcn": dict(LAYERS, kernel=kernel, latency=False, importance=True, in_feat=3, stages=1,
+                           dilation=[1] * 9)}
+    torch.manual_seed(0)
+    m = P.MODELS["co-st-gcn"](rank=None, **arch).to(dev).eval().set_compute_dtype(dtype)
+    gen = torch.Generator(device=dev).manual_seed(5)
+    with torch.no_grad():
+        sb, dst = m.stream_batch(B), m.stream_batch(B)
+        # heads everywhere: stream b has consumed 3 b + 1 frames
+        sb.step_clip(torch.randn(B, 3, 3 * B + 1, 25, device=dev, generator=gen), None, [3 * b + 1 for b in range(B)])
+        snap = sb.export_state()
+        slots = torch.arange(B, dtype=torch.int32, device=dev)  # import's targets, read on the device
+        # each call captured once and replayed: HIP events then bracket device work, not the host's launch path
+        export_ms = _timed(_capture(lambda: sb.export_state()), reps)
+        import_ms = _timed(_capture(lambda: dst.import_state(snap, slots)), reps)
+        assert torch.equal(dst.export_state().data, snap.data)
+        clone_ms = _timed(_capture(lambda: snap.data.clone()), reps)
+        out = torch.empty_like(snap.data)
+        V = snap.V
+
+        def torch_export():
+            for b in range(B):
+                heads = torch.stack([idx[b] for _, _, idx in sb.state]).tolist()  # one read-back per stream
+                for (ring, res, _), (C, n0, n1, off0, off1), (i0, i1) in zip(sb.state, snap.layout, heads):
+                    out[b, off0:off1].view(n0, V, C).copy_(ring[b].roll(-i0, 0))
+                    out[b, off1:off1 + n1 * V * C].view(n1, V, C).copy_(res[b].roll(-i1, 0))
+
+        def torch_import():
+            for b in range(B):
+                for (ring, res, idx), (C, n0, n1, off0, off1) in zip(dst.state, snap.layout):
+                    ring[b].copy_(snap.data[b, off0:off1].view(n0, V, C))
+                    res[b].copy_(snap.data[b, off1:off1 + n1 * V * C].view(n1, V, C))
+                    idx[b].zero_()
+
+        torch_export_ms = _dev_ms(torch_export, 3, warm=1)
+        assert torch.equal(out, snap.data)
+        torch_import_ms = _dev_ms(torch_import, 3, warm=1)
+        assert torch.equal(dst.export_state().data, snap.data)
+    nbytes = snap.data.numel() * 4
+    row = {"config": f"co-st-gcn stream snapshots (stgcn_stream_state_export / _import), ln/costgcn_local.json widths, "
+                     f"Kt={kernel}: all B streams, one launch each way",
+           "dtype": dtype, "Kt": kernel, "B": B, "snapshot_bytes": nbytes, "state_bytes": sb.state_bytes,
+           "export_device_ms": round(export_ms, 4), "import_device_ms": round(import_ms, 4),
+           "clone_device_ms": round(clone_ms, 4), "torch_export_ms": round(torch_export_ms, 3),
+           "torch_import_ms": round(torch_import_ms, 3),
+           "export_over_clone": round(export_ms / clone_ms, 3), "import_over_clone": round(import_ms / clone_ms, 3),
+           "export_over_torch": round(export_ms / torch_export_ms, 5),
+           "import_over_torch": round(import_ms / torch_import_ms, 5),
+           "export_snapshot_GBps": round(nbytes / export_ms / 1e6, 1),
+           "note": f"export, import and clone: HIP events around {reps} replays of the captured call; the torch "
+                   "composition: HIP events around 3 eager runs, its B host read-backs included; no per-kernel trace"}
+    del sb, dst, snap, out
+    torch.cuda.empty_cache()
+    return row
+
+
 MS_TCN = {"latency": False, "importance": True, "stages": 3, "layers": [10, 10, 10], "kernel": [3, 3, 3],
           "filters": [64, 64, 64], "dropout": [0, 0, 0]}
 MSGCN_ARCH = {"strategy": "spatial", "receptive_field": 50, "segment": 2000, "in_feat": 3, "stages": 4,
@@ -823,6 +889,13 @@ def main():
             for row in rt_streams_clip(P, dev):
                 print(json.dumps(row), flush=True)
                 f.write(json.dumps(row) + "\n")
+    if args.only == "stream_state":
+        with open(os.path.join(ROOT, "profiles", "stream_state.jsonl"), "a") as f:
+            for kernel in (9, 69):
+                for dtype in ("fp32", "bf16"):
+                    row = stream_state(P, dev, kernel, dtype)
+                    print(json.dumps(row), flush=True)
+                    f.write(json.dumps(row) + "\n")
     if args.only == "co":
         for kernel in (9, 69):
             for dtype in ("fp32", "bf16"):
