@@ -39,8 +39,9 @@ extern "C" {
  *      still 7: stgcn_rt_streams_desc.pad_ became dtype (0 = fp32, what a zero-filled descriptor always passed; 1 = bf16
  *      conv operands), stgcn_rt_streams_layer.wp / wrp became const void* of that element type, and
  *      stgcn_rt_streams_pack_weight_as was added — no size, offset or existing entry point changed;
- *      still 7: stgcn_co_clip* added (co_clip.hip) — additive likewise;
- *      still 7: stgcn_co_streams_clip* added (co_streams_clip.hip) — additive likewise;
+ *      still 7: stgcn_co_clip* added — additive likewise;
+ *      still 7: stgcn_co_streams_clip* added (co_streams_clip.hip) — additive likewise; stgcn_co_clip* are since
+ *      served by the same file as its B = 1 case and the two layer structs are one type — no layout changed;
  *      still 7: stgcn_rt_streams_clip* added (rt_streams_clip.hip) — additive likewise;
  *      still 7: stgcn_stream_state* added (stream_state.hip) — additive likewise. */
 #define STGCN_ABI_VERSION 7
@@ -664,31 +665,18 @@ int stgcn_co_streams_splits(const stgcn_co_streams_desc* d, int layer);
 long stgcn_co_streams_workspace(const stgcn_co_streams_desc* d, int layer);
 int stgcn_co_streams(const stgcn_co_streams_desc* d, void* stream);
 
-/* CoST-GCN clip inference (co_clip.hip): T consecutive frames of ONE stream per call, on the rings stgcn_co_layer's
- * calls use (ring, res_ring, idx: the same buffers, the same layout).  The contract:
+/* CoST-GCN clip inference: T consecutive frames of ONE stream per call, on the rings stgcn_co_layer's calls use
+ * (ring, res_ring, idx: the same buffers, the same layout).  The contract:
  *   1. out[t] is what the per-frame calls would give for frame t, the T frames fed one at a time from the state the
  *      rings hold on entry (equal within rounding: the sums below have an order of their own);
  *   2. on return the rings and idx are what those T calls would have left: new frame t in ring slot
  *      (idx0 - 1 - t) mod fifo, its residual row in res_ring slot (idx1 - 1 - t) mod R, idx moved by -T (mod fifo, R);
  *   3. per-frame calls, clips of any T and a re-initialisation of the rings by the caller can be mixed on one stream.
- * Per clip: an input head and an output head per frame, and per layer five launches, every hand-off a kernel boundary,
- * no atomics, no workgroup waiting on another:
- *   gcn    : z_buf[t], r_buf[t] as stgcn_co_streams computes them for a stream (packed wp / wrp)
- *   push   : hist[fifo-1+t] = ReLU(LN1(z_buf[t])) (dtype elements), resq[Kt/2+t] = the residual row of frame t; the
- *            same launch copies the fifo-1 newest ring frames and the Kt/2 newest res_ring rows, oldest first, into
- *            hist[0 .. fifo-1) and resq[0 .. Kt/2).  It is the only launch that reads the rings and writes none.
- *   taps   : partial[t][s][v][co] = sum over K split s of wt . hist, tap k of frame t = hist[fifo-1 + t - k*S]: one
- *            GEMM with T*V dense rows; a workgroup holds 4 row tiles of 32 against one load of each weight fragment
- *   finish : y[t] = relu(LN2(bt + sum_s partial[t][s]) + resq[t]); idx advanced
- *   state  : the last min(T, fifo) hist frames and min(T, Kt/2+1) resq rows into their ring slots.  It is the only
- *            launch that writes the rings, and it runs after the taps and finish launches: a new frame never replaces
- *            a carried frame that an earlier frame of the clip still has to read.
- * Order of every sum: the 16-element k-steps of a K split in sequence within a wave (with Cout < 256 the 8 / (Cout/32)
- * waves of a column tile interleave the split's k-steps and are summed in index order), then the splits in index
- * order, then bt; LayerNorm statistics as in the per-frame calls (two passes, 1024 threads, fixed order).  The split
- * count is a function of (Cout, Kt) alone (stgcn_co_clip_splits; layers[l].splits > 0 forces it), never of T or the
- * device.  Hence chunk invariance: a clip of T frames and any split of it into consecutive clips (T = 1 included)
- * give the same bits in out, ring, res_ring and idx; a captured graph of a clip replays bit-identically.
+ * It is the B = 1 case of stgcn_co_streams_clip (below, co_streams_clip.hip): the same launches, 2 + 5 L of them, on
+ * this descriptor's pointers, with no codes and no lengths: the stream advances by all T frames from the state as it
+ * is.  The stages, the order of every sum and the split count (stgcn_co_clip_splits) are described there.  Hence
+ * chunk invariance: a clip of T frames and any split of it into consecutive clips (T = 1 included) give the same bits
+ * in out, ring, res_ring and idx; a captured graph of a clip replays bit-identically.
  * x: the (3, T, V) fp32 clip, channel c of frame t at x[c * x_stride + t * V] (x_stride >= T * V: a dense clip has
  * x_stride = T * V, a chunk of a longer clip keeps the whole clip's stride).  out: [T][K].
  * wt: stgcn_co_pack_weight's image; wp / wrp: stgcn_rt_streams_pack_weight's (groups = P / 1), fp32.
@@ -699,6 +687,7 @@ int stgcn_co_streams(const stgcn_co_streams_desc* d, void* stream);
  * buffers of different layers may alias each other (each is dead once its layer's state launch has run), except y of
  * neighbouring layers. */
 #define STGCN_CO_CLIP_MAX_T 256
+/* A layer of either clip descriptor; B = 1 for stgcn_co_clip. */
 typedef struct {
   int Cin, Cout, P, Kt, S, res_mode, splits, pad_;
   const float* A;       /* [P][V][V] graph * importance */
@@ -714,16 +703,17 @@ typedef struct {
   const float* lnr_b;
   const void* wt;       /* packed tcn.2 weight, dtype elements */
   const float* bt;      /* [Cout] tcn.2 bias or NULL */
-  void* ring;           /* [fifo][V][Cout] dtype elements: the stream's state, as in stgcn_co_layer */
-  float* res_ring;      /* [Kt/2+1][V][Cout] */
-  int* idx;             /* int[2] */
-  float* z_buf;         /* [T][V][Cout] scratch */
-  float* r_buf;         /* [T][V][Cout] scratch (res_mode 2) */
-  void* hist;           /* [fifo-1 + T][V][Cout] scratch, dtype elements */
-  float* resq;          /* [Kt/2 + T][V][Cout] scratch */
-  float* partial;       /* [T][splits][V][Cout] scratch */
-  float* y;             /* [T][V][Cout] the layer's output rows */
+  void* ring;           /* [B][fifo][V][Cout] dtype elements: the state, as in stgcn_co_layer / _co_streams_layer */
+  float* res_ring;      /* [B][Kt/2+1][V][Cout] */
+  int* idx;             /* [B][2] */
+  float* z_buf;         /* [B][T][V][Cout] scratch */
+  float* r_buf;         /* [B][T][V][Cout] scratch (res_mode 2) */
+  void* hist;           /* [B][fifo-1 + T][V][Cout] scratch, dtype elements */
+  float* resq;          /* [B][Kt/2 + T][V][Cout] scratch */
+  float* partial;       /* [B][T][splits][V][Cout] scratch */
+  float* y;             /* [B][T][V][Cout] the layer's output rows */
 } stgcn_co_clip_layer;
+typedef stgcn_co_clip_layer stgcn_co_streams_clip_layer;
 typedef struct {
   int T, V, L, C0, K, dtype;
   long x_stride;        /* elements between two channels of x */
@@ -744,9 +734,26 @@ int stgcn_co_clip(const stgcn_co_clip_desc* d, void* stream);
 
 /* CoST-GCN clip inference for B independent streams (co_streams_clip.hip): one call advances stream b by n_b frames,
  * on the stream-major state of stgcn_co_streams (ring [B][fifo][V][Cout], res_ring [B][Kt/2+1][V][Cout], idx [B][2]:
- * the same buffers, so per-frame ticks and clips mix on one batch).  Per stream it is stgcn_co_clip: the same stages,
- * the same order of every sum, the same split counts (stgcn_co_streams_clip_splits: a function of (Cout, Kt) and
- * layers[l].splits alone, never of B, T or t0), so a stream's out, ring, res_ring and idx are bit-identical to
+ * the same buffers, so per-frame ticks and clips mix on one batch).  Per stream the contract is stgcn_co_clip's, with
+ * n_b in the place of T.  Per call: an input head and an output head per frame, and per layer five launches, every
+ * hand-off a kernel boundary, no atomics, no workgroup waiting on another:
+ *   gcn    : z_buf[b][t], r_buf[b][t] as stgcn_co_streams computes them for a stream (packed wp / wrp)
+ *   push   : hist[b][fifo-1+t] = ReLU(LN1(z_buf[b][t])) (dtype elements), resq[b][Kt/2+t] = the residual row of frame
+ *            t; the same launch copies the fifo-1 newest ring frames and the Kt/2 newest res_ring rows, oldest first,
+ *            into hist[b][0 .. fifo-1) and resq[b][0 .. Kt/2).  It is the only launch that reads the rings and writes
+ *            none.
+ *   taps   : partial[b][t][s][v][co] = sum over K split s of wt . hist, tap k of frame t = hist[b][fifo-1 + t - k*S]:
+ *            one GEMM with n_b*V dense rows per stream; a workgroup holds 4 row tiles of 32 against one load of each
+ *            weight fragment
+ *   finish : y[b][t] = relu(LN2(bt + sum_s partial[b][t][s]) + resq[b][t]); idx[b] advanced
+ *   state  : the last min(n_b, fifo) hist frames and min(n_b, Kt/2+1) resq rows into their ring slots.  It is the only
+ *            launch that writes the rings, and it runs after the taps and finish launches: a new frame never replaces
+ *            a carried frame that an earlier frame of the clip still has to read.
+ * Order of every sum: the 16-element k-steps of a K split in sequence within a wave (with Cout < 256 the 8 / (Cout/32)
+ * waves of a column tile interleave the split's k-steps and are summed in index order), then the splits in index
+ * order, then bt; LayerNorm statistics as in the per-frame calls (two passes, 1024 threads, fixed order).  The split
+ * count (stgcn_co_streams_clip_splits, stgcn_co_clip_splits) is a function of (Cout, Kt) and layers[l].splits (> 0
+ * forces it) alone, never of B, T, t0 or the device.  So a stream's out, ring, res_ring and idx are bit-identical to
  * stgcn_co_clip's on the same frames from the same state, whatever B, its slot, T, the other streams' codes, lengths
  * and contents, and however the frames are split into consecutive calls.
  * active [B] and lengths [B] are device int32, read by the kernels (a captured call replays with other values):
@@ -759,37 +766,11 @@ int stgcn_co_clip(const stgcn_co_clip_desc* d, void* stream);
  * t0 is the position of this call's first frame in the caller's clip: a clip longer than T runs as consecutive calls
  * with t0 = 0, T, 2T, ..., x and out moved on by the caller, lengths and active unchanged.
  * out rows t >= n_b are written as zeros.  Launches: 2 + 5 L whatever B and T are, grids sized from (B, T); a workgroup
- * whose frame, row tile or ring slot lies beyond n_b returns after reading the code and the length.  push is the only
- * launch that reads rings and writes none; state is the only launch that writes rings; taps and finish lie between.
+ * whose frame, row tile or ring slot lies beyond n_b returns after reading the code and the length.
  * x: stream b's channel c of frame t at x[b * x_bstride + c * x_stride + t * V]; out: stream b's row t at
  * out[b * out_bstride + t * K].  Scratch is stream-major; different layers' scratch may alias as in stgcn_co_clip.
  * Limits are stgcn_co_clip's plus B >= 1; anything else, or a NULL required pointer (active and lengths included),
  * returns 1 (2 for the dtype) before any launch; the two queries return -1. */
-typedef struct {
-  int Cin, Cout, P, Kt, S, res_mode, splits, pad_;
-  const float* A;       /* [P][V][V] graph * importance */
-  const float* wp;      /* packed gcn.conv weight, as in stgcn_co_clip_layer */
-  const float* bias2d;  /* [V][Cout] or NULL */
-  const float* wrp;     /* packed residual.0 weight (res_mode 2) */
-  const float* br;      /* [Cout] or NULL */
-  const float* ln1_w;   /* tcn.0, (C,1,V) as stored */
-  const float* ln1_b;
-  const float* ln2_w;   /* tcn.3 */
-  const float* ln2_b;
-  const float* lnr_w;   /* residual.1 (res_mode 2) */
-  const float* lnr_b;
-  const void* wt;       /* packed tcn.2 weight, dtype elements */
-  const float* bt;      /* [Cout] tcn.2 bias or NULL */
-  void* ring;           /* [B][fifo][V][Cout] dtype elements: the batch's state, as in stgcn_co_streams_layer */
-  float* res_ring;      /* [B][Kt/2+1][V][Cout] */
-  int* idx;             /* [B][2] */
-  float* z_buf;         /* [B][T][V][Cout] scratch */
-  float* r_buf;         /* [B][T][V][Cout] scratch (res_mode 2) */
-  void* hist;           /* [B][fifo-1 + T][V][Cout] scratch, dtype elements */
-  float* resq;          /* [B][Kt/2 + T][V][Cout] scratch */
-  float* partial;       /* [B][T][splits][V][Cout] scratch */
-  float* y;             /* [B][T][V][Cout] the layer's output rows */
-} stgcn_co_streams_clip_layer;
 typedef struct {
   int B, T, t0, V, L, C0, K, dtype;
   long x_stride;        /* elements between two channels of x */

@@ -18,14 +18,14 @@ Scope: LayerNorm only (the reference's BatchNorm variant takes statistics over w
 inference only, in_feat 3, V <= 32, P <= 3, channels % 4 == 0 and <= 256, odd Kt <= 69, stride 1 or 2.
 
 ``forward_clip(x (1, in_feat, T, V)) -> (1, num_classes, T)`` advances the same stream by T frames in one call
-(co_clip.hip): every layer's temporal conv becomes one GEMM with T*V rows that reads the tap weights once per clip.
+(stgcn_co_clip): every layer's temporal conv becomes one GEMM with T*V rows that reads the tap weights once per clip.
 Its columns and the state it leaves are those of T ``forward`` calls within rounding, and bit for bit those of any
 other chunking of the same frames through ``forward_clip``.
 
 ``Model.stream_batch(B)`` serves B independent streams per call (CoStreamBatch, co_streams.hip) with state of its own;
 ``forward`` stays the call for one stream.  ``CoStreamBatch.step_clip(x (B, in_feat, T, V), active, lengths)`` is the
 two together: stream b advances by lengths[b] frames in one call (co_streams_clip.hip), bit for bit as
-``forward_clip`` would advance it.
+``forward_clip``, its B = 1 case, would advance it.
 """
 from __future__ import annotations
 
@@ -87,6 +87,39 @@ def _fill_layer(y, l, A_eff, keep, dt):
     y.ln1_w, y.ln1_b = keep(LF._flat_ln(l.tcn[0].weight)), keep(LF._flat_ln(l.tcn[0].bias))
     y.ln2_w, y.ln2_b = keep(LF._flat_ln(l.tcn[3].weight)), keep(LF._flat_ln(l.tcn[3].bias))
     y.wt, y.bt = keep(K.co_pack_weight(l.tcn[2].weight, dt)), keep(f32(l.tcn[2].bias))
+
+
+# the layer fields a clip descriptor takes over from the per-frame descriptor it is built beside (CoLayer,
+# CoStreamsLayer): shapes, parameters and state
+CLIP_LAYER_FIELDS = ("Cin", "Cout", "P", "Kt", "S", "res_mode", "A", "bias2d", "br", "ln1_w", "ln1_b", "ln2_w", "ln2_b",
+                     "lnr_w", "lnr_b", "wt", "bt", "ring", "res_ring", "idx")
+
+
+def _clip_scratch(d, B, layers, dt, dev, workspace):
+    """The scratch of clip descriptor ``d`` (CoClipDesc with B = 1, CoStreamsClipDesc; shapes, T and the layers' forced
+    splits filled in) for B streams of d.T frames: every layer's split count by ``workspace`` (the descriptor's
+    K.co_*clip_workspace, which raises on unsupported shapes), then h0, z, r, two alternating y, hist (``dt``
+    elements), resq and the split partials, stream-major, each sized for the largest layer and shared by all.
+    Assigns them and returns the keep-alive list."""
+    nbytes = []
+    for i in range(d.L):
+        d.layers[i].splits, nb = workspace(d, i)
+        nbytes.append(nb)
+    keep = Keep()
+
+    def buf(n, dtype=torch.float32):
+        return keep(torch.empty(B * n, dtype=dtype, device=dev))
+
+    cap, V, cmax = d.T, d.V, max(l.out_channels for l in layers)
+    d.h0 = buf(cap * V * d.C0)
+    z, r, ys = buf(cap * V * cmax), buf(cap * V * cmax), (buf(cap * V * cmax), buf(cap * V * cmax))
+    hist = buf(max((l.fifo_size - 1 + cap) * V * l.out_channels for l in layers), dt)
+    resq = buf(max((l.gamma // 2 + cap) * V * l.out_channels for l in layers))
+    partial = keep(K._workspace(max(nbytes), dev))
+    for i in range(d.L):
+        y = d.layers[i]
+        y.z_buf, y.r_buf, y.hist, y.resq, y.partial, y.y = z, r, hist, resq, partial, ys[i & 1]
+    return keep
 
 
 class Model(nn.Module):
@@ -258,38 +291,19 @@ class Model(nn.Module):
             d = K.L.CoClipDesc()
             d.T, d.V, d.L, d.C0, d.K = cap, V, len(layers), self.fcn_in.out_channels, self.fcn_out.out_channels
             d.dtype = K.L.dtype_code(dt)
-            for y, c in zip(d.layers, plan["descs"]):
-                y.Cin, y.Cout, y.P, y.Kt, y.S, y.res_mode, y.splits = c.Cin, c.Cout, c.P, c.Kt, c.S, c.res_mode, self.k_splits
-            nbytes = []
-            for i in range(d.L):
-                d.layers[i].splits, nb = K.co_clip_workspace(d, i)
-                nbytes.append(nb)
-            p = keep = Keep()
-            fill_heads(d, self, keep)
-            cmax = max(l.out_channels for l in layers)
-
-            def buf(n, dtype=torch.float32):
-                return p(torch.empty(n, dtype=dtype, device=dev))
-
-            d.h0 = buf(cap * V * d.C0)
-            z, r, ys = buf(cap * V * cmax), buf(cap * V * cmax), (buf(cap * V * cmax), buf(cap * V * cmax))
-            hist = buf(max((l.fifo_size - 1 + cap) * V * l.out_channels for l in layers), dt)
-            resq = buf(max((l.gamma // 2 + cap) * V * l.out_channels for l in layers))
-            partial = p(K._workspace(max(nbytes), dev))
-            for i, (y, c) in enumerate(zip(d.layers, plan["descs"])):
-                for n in ("A", "bias2d", "br", "ln1_w", "ln1_b", "ln2_w", "ln2_b", "lnr_w", "lnr_b", "wt", "bt", "ring",
-                          "res_ring", "idx"):
+            for y, c, (wp, wrp) in zip(d.layers, plan["descs"], plan["clip_packs"]):
+                for n in CLIP_LAYER_FIELDS:
                     setattr(y, n, getattr(c, n))
-                wp, wrp = plan["clip_packs"][i]
-                y.wp, y.wrp = wp.data_ptr(), K.L.ptr(wrp)
-                y.z_buf, y.r_buf, y.hist, y.resq, y.partial, y.y = z, r, hist, resq, partial, ys[i & 1]
+                y.splits, y.wp, y.wrp = self.k_splits, wp.data_ptr(), K.L.ptr(wrp)
+            keep = _clip_scratch(d, 1, layers, dt, dev, K.co_clip_workspace)
+            fill_heads(d, self, keep)
         clips[cap] = (d, keep)
         return d
 
     def forward_clip(self, x):
         """x (1, in_feat, T, V), T >= 1 -> (1, num_classes, T) fp32: column t is what ``forward`` would return for
         frame t, the frames fed one at a time from the stream's current state, and the state afterwards is what those
-        T calls would have left (stgcn_co_clip, co_clip.hip: every layer's temporal conv as one GEMM over the clip).
+        T calls would have left (stgcn_co_clip: every layer's temporal conv as one GEMM over the clip).
         ``forward``, ``forward_clip`` and ``reset_state()`` mix freely on one stream.  Clips longer than ``clip_chunk``
         frames run in chunks; any chunking, T = 1 pieces included, gives the same bits."""
         if torch.is_grad_enabled() and any(q.requires_grad for q in self.parameters()):
@@ -347,8 +361,8 @@ class CoStreamBatch(StreamBatch):
     ring, residual ring and indices for every layer, and ``step`` advances the active ones by one frame
     (stgcn_co_streams, co_streams.hip: the tap GEMM runs groups of streams against one read of the weights).  Follows
     the model's ``compute_dtype``: fp32, or bf16 tap weights and rings.  ``step_clip`` advances stream b by up to T
-    frames per call on the same state (stgcn_co_streams_clip, co_streams_clip.hip); its scratch is bounded by
-    ``clip_frames``.
+    frames per call on the same state (stgcn_co_streams_clip, co_streams_clip.hip), bit for bit as
+    ``Model.forward_clip`` would on the same frames from the same state; its scratch is bounded by ``clip_frames``.
 
     The state buffers live here (``state``: per layer (ring, res_ring, idx); ``state_bytes`` / ``scratch_bytes``: what
     was allocated) and survive a rebuild of the weight packs and the descriptor, which follows ``Model._key()``.  An
@@ -364,9 +378,6 @@ class CoStreamBatch(StreamBatch):
         if len(model.gcn_networks) > K.L.RT_MAX_LAYERS:
             raise RuntimeError(f"stgcn_amd: co-st-gcn supports at most {K.L.RT_MAX_LAYERS} layers")
         self.splits, self._scratch, self._dtype = int(splits), None, None
-        self.clip_frames = 1024  # step_clip's scratch bound: B * (frames per chunk) stays at or below this
-        self._clips = (None, {})  # (the pack the descriptors point into, {frame capacity: (descriptor, keep, bytes)})
-        self._full = torch.full((self.B,), 2 ** 30, dtype=torch.int32, device=model.A.device)  # lengths=None
         self._desc()
 
     # ------------------------------------------------------------------ buffers: once per (device, compute dtype)
@@ -409,7 +420,7 @@ class CoStreamBatch(StreamBatch):
     @property
     def scratch_bytes(self):
         """What was allocated beside the state: ``step``'s scratch, and ``step_clip``'s for every frame capacity used."""
-        return self._step_bytes + sum(nbytes for _, _, nbytes in self._clips[1].values())
+        return self._step_bytes + super().scratch_bytes
 
     def _desc(self):
         m = self.model
@@ -440,93 +451,23 @@ class CoStreamBatch(StreamBatch):
         with K.device_of(x):
             return K.co_streams(d, x, active, out)
 
-    # ------------------------------------------------------------------ clips: n_b frames of stream b per call
-    def _clip_chunk(self):
-        """Frames per stgcn_co_streams_clip call: B * chunk <= clip_frames, a power of two, at most CO_CLIP_MAX_T."""
-        n = min(K.L.CO_CLIP_MAX_T, max(1, int(self.clip_frames) // self.B))
-        return 1 << (n.bit_length() - 1)
+    # ------------------------------------------------------------------ clips: stgcn_co_streams_clip
+    CLIP_MAX_T = K.L.CO_CLIP_MAX_T
+    _launch_clip = staticmethod(K.co_streams_clip)
 
-    def _clip_desc(self, T):
-        """The stgcn_co_streams_clip_desc for calls of up to T <= chunk frames: the state, weight packs and norm affines
-        of ``_desc()``'s descriptor plus stream-major scratch for the next power of two >= T, shared by every layer.
-        One descriptor per capacity is kept with the batch until the packs are rebuilt, so a captured call keeps its
-        buffers."""
+    def _build_clip_desc(self, cap):
+        """The stgcn_co_streams_clip_desc for calls of up to ``cap`` frames: ``_desc()``'s heads, split counts, packs
+        and state, plus ``_clip_scratch`` for B streams."""
         d0, _ = self._desc()
-        if self._clips[0] is not self._pack:
-            self._clips = (self._pack, {})
-        cap = min(self._clip_chunk(), 1 << (T - 1).bit_length())
-        clips = self._clips[1]
-        if cap in clips:
-            return clips[cap][0]
-        m, B, V = self.model, self.B, self.V
-        dev, dt, layers = m.A.device, m.compute_dtype, m.gcn_networks
-        with K.device_of(m.A):
-            d = K.L.CoStreamsClipDesc()
-            d.B, d.T, d.V, d.L, d.C0, d.K, d.dtype = B, cap, V, d0.L, d0.C0, d0.K, d0.dtype
-            for n in ("ln_w", "ln_b", "w_in", "b_in", "w_out", "b_out"):
-                setattr(d, n, getattr(d0, n))
-            for y, c in zip(d.layers, d0.layers):
-                for n in ("Cin", "Cout", "P", "Kt", "S", "res_mode", "splits", "A", "wp", "bias2d", "wrp", "br", "ln1_w",
-                          "ln1_b", "ln2_w", "ln2_b", "lnr_w", "lnr_b", "wt", "bt", "ring", "res_ring", "idx"):
-                    setattr(y, n, getattr(c, n))
-            nbytes = [K.co_streams_clip_workspace(d, i)[1] for i in range(d.L)]
-            keep = Keep()
-
-            def buf(n, dtype=torch.float32):
-                return keep(torch.empty(n, dtype=dtype, device=dev))
-
-            cmax = max(l.out_channels for l in layers)
-            d.h0 = buf(B * cap * V * d.C0)
-            z, r, ys = buf(B * cap * V * cmax), buf(B * cap * V * cmax), (buf(B * cap * V * cmax), buf(B * cap * V * cmax))
-            hist = buf(B * max((l.fifo_size - 1 + cap) * V * l.out_channels for l in layers), dt)
-            resq = buf(B * max((l.gamma // 2 + cap) * V * l.out_channels for l in layers))
-            partial = keep(K._workspace(max(nbytes), dev))
-            for i in range(d.L):
-                y = d.layers[i]
-                y.z_buf, y.r_buf, y.hist, y.resq, y.partial, y.y = z, r, hist, resq, partial, ys[i & 1]
-        clips[cap] = (d, keep, sum(t.numel() * t.element_size() for t in keep))
-        return d
-
-    def step_clip(self, x, active=None, lengths=None):
-        """x (B, 3, T, V), T >= 1 -> (B, num_classes, T) fp32: stream b consumes frames 0 .. n_b - 1, n_b =
-        clamp(lengths[b], 0, T).  Column t < n_b of stream b is what ``step`` would return for that frame, the frames
-        fed one tick at a time from the stream's current state, and its rings and indices end where those n_b ticks
-        would have left them; columns t >= n_b, and every column of a skipped stream, are zero
-        (stgcn_co_streams_clip, co_streams_clip.hip).  ``active`` as in ``step`` (code 2: ``reset([b])`` first, on the
-        device).  ``lengths``: None (all T frames), an int32 device tensor [B] used as given with no host sync, or a host
-        sequence.  Both are read on the device, so a captured call replays with other codes and lengths.
-
-        A stream's outputs and state are bit-identical whatever B, its slot, T, the other streams and the chunking into
-        consecutive ``step_clip`` calls are, and bit-identical to ``Model.forward_clip`` on the same frames from the
-        same state.  ``step``, ``step_clip`` and ``reset`` mix freely.  Calls run in chunks of
-        min(CO_CLIP_MAX_T, clip_frames // B) frames (a power of two), which bounds the scratch."""
-        B, V = self.B, self.V
-        if x.dim() != 4 or x.shape[0] != B or x.shape[1] != 3 or x.shape[2] < 1 or x.shape[3] != V:
-            raise RuntimeError(f"stgcn_amd: CoStreamBatch.step_clip expects x of shape ({B}, 3, T >= 1, {V}), got "
-                               f"{tuple(x.shape)}")
-        for name, a in (("active", active), ("lengths", lengths)):
-            if a is not None and (len(a) if not torch.is_tensor(a) else (a.shape[0] if a.dim() == 1 else -1)) != B:
-                raise RuntimeError(f"stgcn_amd: CoStreamBatch.step_clip expects {name} of shape ({B},)")
-        if int(self.clip_frames) < 1:
-            raise RuntimeError(f"stgcn_amd: CoStreamBatch.clip_frames must be >= 1, got {self.clip_frames}")
-        K.L.require_device(x)
-        x = K._f32c(x)
-        codes = []
-        for a, default in ((active, self._all), (lengths, self._full)):
-            if a is None:
-                a = default
-            elif not (torch.is_tensor(a) and a.dtype == torch.int32 and a.is_cuda):
-                a = torch.as_tensor(a).to(device=x.device, dtype=torch.int32)
-            codes.append(a.contiguous())
-        T, chunk = x.shape[2], self._clip_chunk()
-        with torch.no_grad():
-            d0, _ = self._desc()
-            out = torch.empty((B, T, d0.K), dtype=torch.float32, device=x.device)
-            with K.device_of(x):
-                for t0 in range(0, T, chunk):
-                    n = min(chunk, T - t0)
-                    K.co_streams_clip(self._clip_desc(n), x, t0, n, codes[0], codes[1], out)
-        return out.transpose(1, 2)
+        m = self.model
+        d = K.L.CoStreamsClipDesc()
+        d.B, d.T, d.V, d.L, d.C0, d.K, d.dtype = self.B, cap, self.V, d0.L, d0.C0, d0.K, d0.dtype
+        for n in ("ln_w", "ln_b", "w_in", "b_in", "w_out", "b_out"):
+            setattr(d, n, getattr(d0, n))
+        for y, c in zip(d.layers, d0.layers):
+            for n in CLIP_LAYER_FIELDS + ("splits", "wp", "wrp"):
+                setattr(y, n, getattr(c, n))
+        return d, _clip_scratch(d, self.B, m.gcn_networks, m.compute_dtype, m.A.device, K.co_streams_clip_workspace)
 
     @torch.no_grad()
     def reset(self, streams=None):

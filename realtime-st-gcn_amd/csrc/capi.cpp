@@ -375,7 +375,7 @@ int stgcn_co_streams(const stgcn_co_streams_desc* d, void* stream) {
 
 int stgcn_co_clip_splits(const stgcn_co_clip_desc* d, int layer) {
   if (!d || co_clip_check(*d, true) != STGCN_OK || layer < 0 || layer >= d->L) return -1;
-  return co_clip_num_splits(*d, layer);
+  return co_clip_num_splits(d->layers[layer]);
 }
 long stgcn_co_clip_workspace(const stgcn_co_clip_desc* d, int layer) {
   const int n = stgcn_co_clip_splits(d, layer);
@@ -389,7 +389,7 @@ int stgcn_co_clip(const stgcn_co_clip_desc* d, void* stream) {
 
 int stgcn_co_streams_clip_splits(const stgcn_co_streams_clip_desc* d, int layer) {
   if (!d || co_streams_clip_check(*d, true) != STGCN_OK || layer < 0 || layer >= d->L) return -1;
-  return co_streams_clip_num_splits(*d, layer);
+  return co_clip_num_splits(d->layers[layer]);
 }
 long stgcn_co_streams_clip_workspace(const stgcn_co_streams_clip_desc* d, int layer) {
   const int n = stgcn_co_streams_clip_splits(d, layer);

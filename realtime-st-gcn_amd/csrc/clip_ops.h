@@ -1,11 +1,10 @@
 // The stages of a co-st-gcn clip (T consecutive frames of one stream, every layer's temporal conv as one causal GEMM) as
-// __device__ functions on ONE stream's buffers.  co_clip.hip (one stream per call: the descriptor's pointers as they
-// are) and co_streams_clip.hip (B streams per call: the pointers offset to stream b, the frame count n_b and the restart
-// flag read on the device) set up the pointers, call these and keep the launch order; the arithmetic and the order of
-// every sum live here once, which is what makes the two routes agree bit for bit.
+// __device__ functions on ONE stream's buffers.  co_streams_clip.hip (B streams per call, one stream's clip as B = 1:
+// the pointers offset to stream b, the frame count n_b and the restart flag read on the device) sets up the pointers,
+// calls these and keeps the launch order; the arithmetic and the order of every sum live here.
 //
-// D is stgcn_co_clip_layer or stgcn_co_streams_clip_layer (the same field names).  n is the number of frames the stream
-// consumes in this call.  hist / resq are the stream's linear clip buffers of co_clip.hip's header comment.
+// D is stgcn_co_clip_layer.  n is the number of frames the stream consumes in this call.  hist / resq are the stream's
+// linear clip buffers of co_streams_clip.hip's header comment.
 #pragma once
 #include "common.h"
 #include "frame_ops.h"

@@ -1,5 +1,5 @@
 // The stages of the per-frame (continual inference) routes: each stage has ONE body here; the __global__ kernels of
-// rt_fused.hip, co_frame.hip, rt_streams.hip, co_streams.hip and co_clip.hip set up pointers, call the stages and
+// rt_fused.hip, co_frame.hip, rt_streams.hip, co_streams.hip and co_streams_clip.hip set up pointers, call the stages and
 // place the barriers between them.  A stage that reduces over the block is a template on the block size NTH (tid-stride loops and
 // block_sum fix the order of its sums), and every kernel instantiates it with its own block size:
 //
@@ -12,7 +12,7 @@
 //   co_finish_stage<NTH>           co_finish_kernel (1024, stream 0), cs_finish_kernel (1024, stream b)
 //   ring_unit / load_ring<T>       cs_taps_kernel<T, TU>; co_taps_kernel<T> keeps its load_a<T>(ring, ...)
 //   ln_stats_units<NTH, U>         rt_streams_kernel (512), the push / finish stages (1024)
-// The clip routes (co_clip.hip, co_streams_clip.hip: frame t of a clip in the place of stream b) go through
+// The co-st-gcn clip route (co_streams_clip.hip: frame t of a clip in the place of stream b) goes through
 // clip_ops.h, which instantiates the heads, conv_tile_acc / amix_*, co_push_stage and ring_unit like co_streams.hip;
 // its finish_frame restates co_finish_stage's arithmetic with the residual row taken from the clip's linear buffer (no
 // ring head to read or store).

@@ -132,13 +132,11 @@ int co_finish_launch(const stgcn_co_layer& d, hipStream_t s);
 int co_streams_check(const stgcn_co_streams_desc& d, bool shapes_only);
 int co_streams_num_splits(const stgcn_co_streams_desc& d, int layer);
 int co_streams_launch(const stgcn_co_streams_desc& d, hipStream_t s);
-// co_clip.hip
+// co_streams_clip.hip: the stream batch's clip, and one stream's as its B = 1 case
+int co_clip_num_splits(const stgcn_co_clip_layer& y);
 int co_clip_check(const stgcn_co_clip_desc& d, bool shapes_only);
-int co_clip_num_splits(const stgcn_co_clip_desc& d, int layer);
 int co_clip_launch(const stgcn_co_clip_desc& d, hipStream_t s);
-// co_streams_clip.hip
 int co_streams_clip_check(const stgcn_co_streams_clip_desc& d, bool shapes_only);
-int co_streams_clip_num_splits(const stgcn_co_streams_clip_desc& d, int layer);
 int co_streams_clip_launch(const stgcn_co_streams_clip_desc& d, hipStream_t s);
 // rt_streams_clip.hip
 int rt_streams_clip_launch(const stgcn_rt_streams_clip_desc& d, hipStream_t s);

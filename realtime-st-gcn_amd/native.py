@@ -1075,15 +1075,22 @@ def co_layer_frame(desc):
     L.check(lib.stgcn_co_finish(d, s), "co_finish")
 
 
+def _co_workspace(entry, desc, layer, what):
+    """(K-split count, bytes of the split partials) of layer ``layer`` of ``desc`` by the two queries of ``entry``
+    (<entry>_splits, <entry>_workspace); raises with ``what`` on shapes the kernels do not take."""
+    n = getattr(L.lib(), entry + "_splits")(ctypes.byref(desc), layer)
+    nbytes = getattr(L.lib(), entry + "_workspace")(ctypes.byref(desc), layer)
+    if n < 1 or nbytes < 0:
+        raise RuntimeError(f"stgcn_amd: co-st-gcn {what}")
+    return n, nbytes
+
+
 def co_streams_workspace(desc, layer):
     """(K-split count, bytes of the split partials) of layer ``layer`` of a stgcn_co_streams_desc (shapes and B
     filled in); raises on shapes the kernels do not take."""
-    n = L.lib().stgcn_co_streams_splits(ctypes.byref(desc), layer)
-    nbytes = L.lib().stgcn_co_streams_workspace(ctypes.byref(desc), layer)
-    if n < 1 or nbytes < 0:
-        raise RuntimeError("stgcn_amd: co-st-gcn stream batch shape not supported (B >= 1, V <= 32, P <= 3, C % 4 == 0, "
-                           f"C <= 256, odd Kt <= 69, stride 1 or 2, at most {L.RT_MAX_LAYERS} layers)")
-    return n, nbytes
+    return _co_workspace("stgcn_co_streams", desc, layer,
+                         "stream batch shape not supported (B >= 1, V <= 32, P <= 3, C % 4 == 0, "
+                         f"C <= 256, odd Kt <= 69, stride 1 or 2, at most {L.RT_MAX_LAYERS} layers)")
 
 
 def co_streams(desc, x, active, out):
@@ -1097,12 +1104,9 @@ def co_streams(desc, x, active, out):
 def co_clip_workspace(desc, layer):
     """(K-split count, bytes of the split partials) of layer ``layer`` of a stgcn_co_clip_desc (shapes and T filled
     in); raises on shapes the kernels do not take."""
-    n = L.lib().stgcn_co_clip_splits(ctypes.byref(desc), layer)
-    nbytes = L.lib().stgcn_co_clip_workspace(ctypes.byref(desc), layer)
-    if n < 1 or nbytes < 0:
-        raise RuntimeError("stgcn_amd: co-st-gcn clip shape not supported (V <= 32, P <= 3, C % 4 == 0, C <= 256, odd "
-                           f"Kt <= 69, stride 1 or 2, at most {L.RT_MAX_LAYERS} layers, 1 <= T <= {L.CO_CLIP_MAX_T})")
-    return n, nbytes
+    return _co_workspace("stgcn_co_clip", desc, layer,
+                         "clip shape not supported (V <= 32, P <= 3, C % 4 == 0, C <= 256, odd "
+                         f"Kt <= 69, stride 1 or 2, at most {L.RT_MAX_LAYERS} layers, 1 <= T <= {L.CO_CLIP_MAX_T})")
 
 
 def co_clip(desc, x, t0, T, out):
@@ -1117,37 +1121,32 @@ def co_clip(desc, x, t0, T, out):
 def co_streams_clip_workspace(desc, layer):
     """(K-split count, bytes of the split partials) of layer ``layer`` of a stgcn_co_streams_clip_desc (shapes, B and T
     filled in); raises on shapes the kernels do not take."""
-    n = L.lib().stgcn_co_streams_clip_splits(ctypes.byref(desc), layer)
-    nbytes = L.lib().stgcn_co_streams_clip_workspace(ctypes.byref(desc), layer)
-    if n < 1 or nbytes < 0:
-        raise RuntimeError("stgcn_amd: co-st-gcn stream batch clip shape not supported (B >= 1, V <= 32, P <= 3, "
-                           f"C % 4 == 0, C <= 256, odd Kt <= 69, stride 1 or 2, at most {L.RT_MAX_LAYERS} layers, "
-                           f"1 <= T <= {L.CO_CLIP_MAX_T})")
-    return n, nbytes
+    return _co_workspace("stgcn_co_streams_clip", desc, layer,
+                         "stream batch clip shape not supported (B >= 1, V <= 32, P <= 3, "
+                         f"C % 4 == 0, C <= 256, odd Kt <= 69, stride 1 or 2, at most {L.RT_MAX_LAYERS} layers, "
+                         f"1 <= T <= {L.CO_CLIP_MAX_T})")
+
+
+def _streams_clip(name, desc, x, t0, T, active, lengths, out):
+    """Frames t0 .. t0+T-1 of the clips x (B, 3, T_all, V) fp32 dense through a stream batch's clip entry
+    ``stgcn_<name>``: stream b takes those below lengths[b]; rows t0 .. t0+T-1 of out (B, T_all, K).  active, lengths
+    (B) int32 on the device; ``desc`` is the batch's clip descriptor."""
+    T_all, V = x.shape[2], x.shape[3]
+    desc.T, desc.t0 = T, t0
+    desc.x_stride, desc.x_bstride, desc.out_bstride = T_all * V, 3 * T_all * V, T_all * out.shape[2]
+    desc.x, desc.out = x.data_ptr() + 4 * t0 * V, out.data_ptr() + 4 * t0 * out.shape[2]
+    desc.active, desc.lengths = active.data_ptr(), lengths.data_ptr()
+    L.check(getattr(L.lib(), "stgcn_" + name)(ctypes.byref(desc), L.stream()), name)
 
 
 def co_streams_clip(desc, x, t0, T, active, lengths, out):
-    """Frames t0 .. t0+T-1 of the clips x (B, 3, T_all, V) fp32 dense through a CoST-GCN stream batch
-    (stgcn_co_streams_clip): stream b takes those below lengths[b]; rows t0 .. t0+T-1 of out (B, T_all, K).  active,
-    lengths (B) int32 on the device; ``desc`` is the batch's stgcn_co_streams_clip_desc (costgcn.CoStreamBatch)."""
-    T_all, V = x.shape[2], x.shape[3]
-    desc.T, desc.t0 = T, t0
-    desc.x_stride, desc.x_bstride, desc.out_bstride = T_all * V, 3 * T_all * V, T_all * out.shape[2]
-    desc.x, desc.out = x.data_ptr() + 4 * t0 * V, out.data_ptr() + 4 * t0 * out.shape[2]
-    desc.active, desc.lengths = active.data_ptr(), lengths.data_ptr()
-    L.check(L.lib().stgcn_co_streams_clip(ctypes.byref(desc), L.stream()), "co_streams_clip")
+    """``_streams_clip`` through stgcn_co_streams_clip on costgcn.CoStreamBatch's stgcn_co_streams_clip_desc."""
+    _streams_clip("co_streams_clip", desc, x, t0, T, active, lengths, out)
 
 
 def rt_streams_clip(desc, x, t0, T, active, lengths, out):
-    """Frames t0 .. t0+T-1 of the clips x (B, 3, T_all, V) fp32 dense through an rt-st-gcn stream batch
-    (stgcn_rt_streams_clip): stream b takes those below lengths[b]; rows t0 .. t0+T-1 of out (B, T_all, K).  active,
-    lengths (B) int32 on the device; ``desc`` is the batch's stgcn_rt_streams_clip_desc (rtstgcn.RtStreamBatch)."""
-    T_all, V = x.shape[2], x.shape[3]
-    desc.T, desc.t0 = T, t0
-    desc.x_stride, desc.x_bstride, desc.out_bstride = T_all * V, 3 * T_all * V, T_all * out.shape[2]
-    desc.x, desc.out = x.data_ptr() + 4 * t0 * V, out.data_ptr() + 4 * t0 * out.shape[2]
-    desc.active, desc.lengths = active.data_ptr(), lengths.data_ptr()
-    L.check(L.lib().stgcn_rt_streams_clip(ctypes.byref(desc), L.stream()), "rt_streams_clip")
+    """``_streams_clip`` through stgcn_rt_streams_clip on rtstgcn.RtStreamBatch's stgcn_rt_streams_clip_desc."""
+    _streams_clip("rt_streams_clip", desc, x, t0, T, active, lengths, out)
 
 
 def stream_state_export(desc):

@@ -437,8 +437,6 @@ class RtStreamBatch(StreamBatch):
                                f"V * C <= 7680, P <= 3, at most {K.L.RT_MAX_LAYERS} layers")
         super().__init__(model, B)
         V, dev = self.V, model.A.device
-        self._clips = (None, {})  # (the pack the descriptors point into, {frame capacity: (descriptor, keep, bytes)})
-        self._full = torch.full((self.B,), 2 ** 30, dtype=torch.int32, device=dev)  # lengths=None
         # state: per layer (fifo [B][fifo][V][C], acc [B][S][V][C], idx [B][2]), fp32 whatever dtype
         for l in model.st_gcn:
             ag = l.aggregate
@@ -478,36 +476,14 @@ class RtStreamBatch(StreamBatch):
     def _launch(self, d, x, active, out):
         return K.rt_streams(d, x, active, out)
 
-    # ------------------------------------------------------------------ clips: n_b frames of stream b per call
-    clip_frames = 1024  # step_clip's scratch bound: B * (frames per chunk) stays at or below this
+    # ------------------------------------------------------------------ clips: stgcn_rt_streams_clip
+    CLIP_MAX_T = K.L.RT_CLIP_MAX_T
+    _launch_clip = staticmethod(K.rt_streams_clip)
 
-    def _clip_chunk(self):
-        """Frames per stgcn_rt_streams_clip call: B * chunk <= clip_frames, a power of two, at most RT_CLIP_MAX_T."""
-        n = min(K.L.RT_CLIP_MAX_T, max(1, int(self.clip_frames) // self.B))
-        return 1 << (n.bit_length() - 1)
-
-    def _clip_calls(self, T):
-        """The calls a clip of T frames runs as: [(t0, frames, scratch capacity)], t0 a multiple of the chunk, the
-        capacity the next power of two >= frames (at most the chunk)."""
-        chunk = self._clip_chunk()
-        return [(t0, min(chunk, T - t0), min(chunk, 1 << (min(chunk, T - t0) - 1).bit_length()))
-                for t0 in range(0, T, chunk)]
-
-    @property
-    def scratch_bytes(self):
-        """What was allocated beside the state: ``step`` needs none; ``step_clip``'s for every frame capacity used."""
-        return sum(nbytes for _, _, nbytes in self._clips[1].values())
-
-    def _clip_desc(self, cap):
-        """The stgcn_rt_streams_clip_desc for calls of up to ``cap`` frames: the state, weight packs and norm rows of
-        ``_desc()``'s descriptor plus stream-major scratch for ``cap`` frames, shared by every layer.  One descriptor
-        per capacity is kept with the batch until the packs are rebuilt, so a captured call keeps its buffers."""
+    def _build_clip_desc(self, cap):
+        """The stgcn_rt_streams_clip_desc for calls of up to ``cap`` frames: ``_desc()``'s heads and layers as they are,
+        plus four stream-major scratch buffers (``step`` itself needs none)."""
         d0, _ = self._desc()
-        if self._clips[0] is not self._pack:
-            self._clips = (self._pack, {})
-        clips = self._clips[1]
-        if cap in clips:
-            return clips[cap][0]
         m, B, V = self.model, self.B, self.V
         dev = m.A.device
         d = K.L.RtStreamsClipDesc()
@@ -523,45 +499,7 @@ class RtStreamBatch(StreamBatch):
         d.xb, d.z, d.a = (keep(torch.empty(n, dtype=torch.float32, device=dev)) for _ in range(3))
         if any(l.is_residual_conv for l in m.st_gcn):
             d.r = keep(torch.empty(n, dtype=torch.float32, device=dev))
-        clips[cap] = (d, keep, sum(t.numel() * t.element_size() for t in keep))
-        return d
-
-    def step_clip(self, x, active=None, lengths=None):
-        """x (B, 3, T, V), T >= 1 -> (B, num_classes, T) fp32: stream b consumes frames 0 .. n_b - 1, n_b =
-        clamp(lengths[b], 0, T).  Column t < n_b of stream b is what ``step`` would return for that frame, the frames
-        fed one tick at a time from the stream's current state, and its FIFO, accumulators and indices end where those
-        n_b ticks would have left them; columns t >= n_b, and every column of a skipped stream, are zero
-        (stgcn_rt_streams_clip, rt_streams_clip.hip).  ``active`` as in ``step`` (code 2: ``reset([b])`` first, on the
-        device).  ``lengths``: None (all T frames), an int32 device tensor [B] used as given with no host sync, or a host
-        sequence.  Both are read on the device, so a captured call replays with other codes and lengths.
-
-        A stream's outputs and state are bit-identical whatever B, its slot, T, the other streams and the chunking into
-        consecutive ``step_clip`` calls are.  ``step``, ``step_clip`` and ``reset`` mix freely.  Calls run in chunks of
-        min(RT_CLIP_MAX_T, clip_frames // B) frames (a power of two), which bounds the scratch."""
-        B, V = self.B, self.V
-        if x.dim() != 4 or x.shape[0] != B or x.shape[1] != 3 or x.shape[2] < 1 or x.shape[3] != V:
-            raise RuntimeError(f"stgcn_amd: RtStreamBatch.step_clip expects x of shape ({B}, 3, T >= 1, {V}), got "
-                               f"{tuple(x.shape)}")
-        for name, a in (("active", active), ("lengths", lengths)):
-            if a is not None and (len(a) if not torch.is_tensor(a) else (a.shape[0] if a.dim() == 1 else -1)) != B:
-                raise RuntimeError(f"stgcn_amd: RtStreamBatch.step_clip expects {name} of shape ({B},)")
-        if int(self.clip_frames) < 1:
-            raise RuntimeError(f"stgcn_amd: RtStreamBatch.clip_frames must be >= 1, got {self.clip_frames}")
-        K.L.require_device(x)
-        x = K._f32c(x)
-        codes = []
-        for a, default in ((active, self._all), (lengths, self._full)):
-            if a is None:
-                a = default
-            elif not (torch.is_tensor(a) and a.dtype == torch.int32 and a.is_cuda):
-                a = torch.as_tensor(a).to(device=x.device, dtype=torch.int32)
-            codes.append(a.contiguous())
-        with torch.no_grad():
-            d0, _ = self._desc()
-            out = torch.empty((B, x.shape[2], d0.K), dtype=torch.float32, device=x.device)
-            for t0, n, cap in self._clip_calls(x.shape[2]):
-                K.rt_streams_clip(self._clip_desc(cap), x, t0, n, codes[0], codes[1], out)
-        return out.transpose(1, 2)
+        return d, keep
 
     def reset(self, streams=None):
         """Zero the FIFO state of the given streams (an iterable of stream indices), or of all of them."""

@@ -254,7 +254,12 @@ def import_streams(kind, B, dtype, state, snap, streams, select, what):
 class StreamBatch:
     """B independent skeleton streams of one per-frame model.  A subclass keeps ``state`` (per layer, a tuple of
     stream-major device tensors), builds its descriptor in ``_desc()`` -> (descriptor, keep-alive list) and launches
-    one tick in ``_launch(d, x, active, out)``."""
+    one tick in ``_launch(d, x, active, out)``.  For ``step_clip`` it gives ``CLIP_MAX_T``, builds a clip descriptor
+    in ``_build_clip_desc(cap)`` -> (descriptor, keep-alive list) and launches one call of up to ``cap`` frames in
+    ``_launch_clip(d, x, t0, n, active, lengths, out)``."""
+
+    CLIP_MAX_T = None  # the most frames the subclass's clip entry takes per call
+    clip_frames = 1024  # step_clip's scratch bound: B * (frames per chunk) stays at or below this
 
     @staticmethod
     def _check_B(B):
@@ -266,7 +271,9 @@ class StreamBatch:
         K.L.require_device(model.A)
         self.model, self.B, self.V = model, int(B), model.A.shape[-1]
         self._all = torch.ones(self.B, dtype=torch.int32, device=model.A.device)
+        self._full = torch.full((self.B,), 2 ** 30, dtype=torch.int32, device=model.A.device)  # lengths=None
         self.state, self._pack = [], None
+        self._clips = (None, {})  # (the pack the descriptors point into, {frame capacity: (descriptor, keep, bytes)})
 
     @property
     def state_bytes(self):
@@ -311,12 +318,85 @@ class StreamBatch:
             raise RuntimeError(f"stgcn_amd: {name}.step expects x of shape {(B, 3, 1, V)}, got {tuple(x.shape)}")
         K.L.require_device(x)
         x = K._f32c(x)
-        if active is None:
-            active = self._all
-        elif not (torch.is_tensor(active) and active.dtype == torch.int32 and active.is_cuda):
-            active = torch.as_tensor(active).to(device=x.device, dtype=torch.int32)
+        active = self._codes(active, self._all, x.device)
         if tuple(active.shape) != (B,) or not active.is_contiguous():
             raise RuntimeError(f"stgcn_amd: {name}.step expects active of shape ({B},)")
         d, _keep = self._desc()
         out = torch.empty((B, d.K, 1), dtype=torch.float32, device=x.device)
         return self._launch(d, x, active, out)
+
+    @staticmethod
+    def _codes(a, default, device):
+        """``active`` / ``lengths`` as the kernels read them: ``default`` for None, an int32 device tensor as given (no
+        host sync), anything else converted on the host."""
+        if a is None:
+            return default
+        if torch.is_tensor(a) and a.dtype == torch.int32 and a.is_cuda:
+            return a
+        return torch.as_tensor(a).to(device=device, dtype=torch.int32)
+
+    # ------------------------------------------------------------------ clips: n_b frames of stream b per call
+    def _clip_chunk(self):
+        """Frames per clip call: B * chunk <= clip_frames, a power of two, at most CLIP_MAX_T."""
+        n = min(self.CLIP_MAX_T, max(1, int(self.clip_frames) // self.B))
+        return 1 << (n.bit_length() - 1)
+
+    def _clip_calls(self, T):
+        """The calls a clip of T frames runs as: [(t0, frames, scratch capacity)], t0 a multiple of the chunk, the
+        capacity the next power of two >= frames (at most the chunk)."""
+        chunk = self._clip_chunk()
+        return [(t0, min(chunk, T - t0), min(chunk, 1 << (min(chunk, T - t0) - 1).bit_length()))
+                for t0 in range(0, T, chunk)]
+
+    @property
+    def scratch_bytes(self):
+        """What was allocated beside the state: ``step_clip``'s scratch for every frame capacity used (a subclass adds
+        what its ``step`` needs)."""
+        return sum(nbytes for _, _, nbytes in self._clips[1].values())
+
+    def _clip_desc(self, cap):
+        """The clip descriptor for calls of up to ``cap`` frames: the state, weight packs and norm parameters of
+        ``_desc()``'s descriptor plus stream-major scratch for ``cap`` frames, shared by every layer.  One descriptor
+        per capacity is kept with the batch until the packs are rebuilt, so a captured call keeps its buffers."""
+        self._desc()
+        if self._clips[0] is not self._pack:
+            self._clips = (self._pack, {})
+        clips = self._clips[1]
+        if cap not in clips:
+            with K.device_of(self.model.A):
+                d, keep = self._build_clip_desc(cap)
+            clips[cap] = (d, keep, sum(t.numel() * t.element_size() for t in keep))
+        return clips[cap][0]
+
+    def step_clip(self, x, active=None, lengths=None):
+        """x (B, 3, T, V), T >= 1 -> (B, num_classes, T) fp32: stream b consumes frames 0 .. n_b - 1, n_b =
+        clamp(lengths[b], 0, T).  Column t < n_b of stream b is what ``step`` would return for that frame, the frames
+        fed one tick at a time from the stream's current state, and its state ends where those n_b ticks would have
+        left it; columns t >= n_b, and every column of a skipped stream, are zero.  ``active`` as in ``step`` (code 2:
+        ``reset([b])`` first, on the device).  ``lengths``: None (all T frames), an int32 device tensor [B] used as
+        given with no host sync, or a host sequence.  Both are read on the device, so a captured call replays with
+        other codes and lengths.
+
+        A stream's outputs and state are bit-identical whatever B, its slot, T, the other streams and the chunking into
+        consecutive ``step_clip`` calls are.  ``step``, ``step_clip`` and ``reset`` mix freely.  Calls run in chunks of
+        min(CLIP_MAX_T, clip_frames // B) frames (a power of two), which bounds the scratch."""
+        B, V, name = self.B, self.V, type(self).__name__
+        if x.dim() != 4 or x.shape[0] != B or x.shape[1] != 3 or x.shape[2] < 1 or x.shape[3] != V:
+            raise RuntimeError(f"stgcn_amd: {name}.step_clip expects x of shape ({B}, 3, T >= 1, {V}), got "
+                               f"{tuple(x.shape)}")
+        for what, a in (("active", active), ("lengths", lengths)):
+            if a is not None and (len(a) if not torch.is_tensor(a) else (a.shape[0] if a.dim() == 1 else -1)) != B:
+                raise RuntimeError(f"stgcn_amd: {name}.step_clip expects {what} of shape ({B},)")
+        if int(self.clip_frames) < 1:
+            raise RuntimeError(f"stgcn_amd: {name}.clip_frames must be >= 1, got {self.clip_frames}")
+        K.L.require_device(x)
+        x = K._f32c(x)
+        active = self._codes(active, self._all, x.device).contiguous()
+        lengths = self._codes(lengths, self._full, x.device).contiguous()
+        with torch.no_grad():
+            d0, _ = self._desc()
+            out = torch.empty((B, x.shape[2], d0.K), dtype=torch.float32, device=x.device)
+            with K.device_of(x):
+                for t0, n, cap in self._clip_calls(x.shape[2]):
+                    self._launch_clip(self._clip_desc(cap), x, t0, n, active, lengths, out)
+        return out.transpose(1, 2)

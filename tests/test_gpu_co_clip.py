@@ -1,7 +1,7 @@
-"""co-st-gcn clips on the device (Model.forward_clip, co_clip.hip): the reference fixtures in one clip and in chunks,
-clips of every critical length mixed with per-frame calls on one stream (outputs and ring state), the reference's widths
-in fp32 and bf16 and route against route, a T > fifo clip at Kt = 69 and full width, graph replay, a parameter change
-mid-stream and the chunk cap.  Bars are test_gpu_costgcn.py's own."""
+"""co-st-gcn clips on the device (Model.forward_clip, stgcn_co_clip): the reference fixtures in one clip and in chunks,
+clips of every critical length mixed with per-frame calls on one stream (outputs and ring state), the clip against a
+stream batch of one, the reference's widths in fp32 and bf16 and route against route, a T > fifo clip at Kt = 69 and
+full width, graph replay, a parameter change mid-stream and the chunk cap.  Bars are test_gpu_costgcn.py's own."""
 import os
 import sys
 
@@ -109,6 +109,38 @@ def test_chunk_invariance_of_state(small):
     assert torch.equal(clips(m, xd, (1, 2, 17, 13)), y)
     for (ring, res, idx), (_, ring2, res2, idx2) in zip(one, m._plan[1]["state"]):
         assert torch.equal(ring, ring2) and torch.equal(res, res2) and torch.equal(idx, idx2)
+
+
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+@pytest.mark.parametrize("T", [1, 4, 5, 8, 9, 10])
+def test_one_stream_is_a_batch_of_one(small, T, dtype):
+    """forward_clip runs the stream batch's kernels with B = 1 and no codes or lengths, so its state launch carries
+    fifo + Kt/2+1 blocks per layer of which those beyond min(T, slots) return.  From a stream 3 frames in, clips whose T
+    straddles the residual ring (5 slots) and the activation ring of the stride-1 layers (9): the outputs against the
+    same frames through forward from the same state (the file's bar), and outputs and state bit for bit against
+    stream_batch(1).step_clip from the snapshot of that state."""
+    m, xd = small["m"], small["xd"]
+    clip = xd[:, :, :T]
+    m.set_compute_dtype(dtype)
+    try:
+        m.reset_state()
+        with torch.no_grad():
+            stream(m, xd[:, :, -3:])
+            snap = m.export_state()
+            y = m.forward_clip(clip)
+            state = m.export_state().data
+            m.import_state(snap)
+            frames = stream(m, clip)
+            sb = m.stream_batch(1)
+            sb.import_state(snap)
+            yb = sb.step_clip(clip)
+            state_b = sb.export_state().data
+        torch.cuda.synchronize()
+    finally:
+        m.set_compute_dtype("fp32")
+    assert_close(y, frames, TOL, f"co-st-gcn {dtype} clip of {T} vs per-frame, 3 frames in")
+    assert torch.equal(y, yb), f"{dtype} clip of {T}: forward_clip vs stream_batch(1).step_clip outputs"
+    assert torch.equal(state, state_b), f"{dtype} clip of {T}: forward_clip vs stream_batch(1).step_clip state"
 
 
 def _rel(y, ref):
