@@ -429,8 +429,9 @@ int stgcn_segment_metrics(const long* labels, const long* pred, int L, int C, co
                           long long* confusion, float* out, int* status, void* stream);
 
 /* RT-ST-GCN per-frame inference (config 3; rt_fused.hip), fp32, batch 1, rows [V][C] of one frame:
- *   stgcn_rt_frame_in  : x (1,3,1,V) -> LayerNorm([3,1,V]) (ln_w/ln_b [3*V], element c*V+v) -> fcn_in
- *                        (w [C0][3], b [C0]) -> out [V][C0]                        (rtstgcn.py:103,140-143)
+ *   stgcn_rt_frame_in_f: x (1,F,1,V) -> LayerNorm([F,1,V]) (ln_w/ln_b [F*V], element c*V+v) -> fcn_in
+ *                        (w [C0][F], b [C0]) -> out [V][C0], 1 <= F <= 16           (rtstgcn.py:103,140-143)
+ *   stgcn_rt_frame_in  : the same with F = 3
  *   stgcn_rt_frame_gcn : OnlineLayer's conv1x1 + A-mix (A [P][V][V] = graph * importance, w [P*Cout][Cin],
  *                        bias2d [V][Cout] = the conv bias through A) and AggregateStgcn's FIFO step
  *                        (fifo [S*(K-1)+1][V][Cout], acc [S][V][Cout], idx int[2] = (fifo, acc) indices,
@@ -441,6 +442,8 @@ int stgcn_segment_metrics(const long* labels, const long* pred, int L, int C, co
  *   stgcn_rt_frame_out : mean over V -> fcn_out (w [K][C], b [K]) -> out [K]          (rtstgcn.py:149-153) */
 int stgcn_rt_frame_in(const float* x, int V, const float* ln_w, const float* ln_b, const float* w, const float* b, int C0,
                       float* out, void* stream);
+int stgcn_rt_frame_in_f(const float* x, int F, int V, const float* ln_w, const float* ln_b, const float* w, const float* b,
+                        int C0, float* out, void* stream);
 int stgcn_rt_frame_gcn(const float* x, int V, int Cin, int Cout, int P, const float* A, const float* w, const float* bias2d,
                        float* fifo, float* acc, const int* idx, const float* wr, float* a_out, float* r_out,
                        void* stream);
@@ -460,6 +463,12 @@ int stgcn_rt_frame_out(const float* x, int V, int C, const float* w, const float
  * status: a device int the kernel sets to 1 if a barrier wait gave up (bounded spin; never reset here).
  * Workgroups of 1024 threads; the hand-off of a / r between workgroups is write-through (sc1) stores and loads.
  * V <= 32, 4 <= C <= 256 (C % 4 == 0), V * C <= 7680, P <= 3, L <= STGCN_RT_MAX_LAYERS, blocks in [1, 256] (0 = 64). */
+/* F, in every descriptor that carries an input head (stgcn_rt_frame_desc, stgcn_rt_streams_desc, stgcn_co_streams_desc,
+ * stgcn_co_clip_desc, stgcn_co_streams_clip_desc, stgcn_rt_streams_clip_desc; additive to ABI 7): the input features per
+ * joint, in_feat of LayerNorm([F,1,V]) and fcn_in.  0 is read as 3, so a zero-initialised descriptor filled as before
+ * the field existed behaves as before; otherwise 1 <= F <= STGCN_MAX_IN_FEAT and F * V >= 2 (the variance is unbiased).
+ * Anything else returns 1 before any launch. */
+#define STGCN_MAX_IN_FEAT 16
 #define STGCN_RT_MAX_LAYERS 12
 typedef struct {
   int Cin, Cout, P, fifo_size, S, res_mode;
@@ -479,10 +488,11 @@ typedef struct {
 } stgcn_rt_layer;
 typedef struct {
   int V, L, C0, K, blocks;
-  const float* x;       /* (1,3,1,V) frame, element c*V+v */
-  const float* ln_w;    /* [3*V] */
+  int F;                /* input features per joint; 0 = 3 */
+  const float* x;       /* (1,F,1,V) frame, element c*V+v */
+  const float* ln_w;    /* [F*V] */
   const float* ln_b;
-  const float* w_in;    /* [C0][3] */
+  const float* w_in;    /* [C0][F] */
   const float* b_in;    /* [C0] */
   const float* w_out;   /* [K][C_last] */
   const float* b_out;   /* [K] or NULL */
@@ -534,11 +544,12 @@ typedef struct {
 typedef struct {
   int V, L, C0, K, B;
   int dtype;            /* conv operand type: 0 fp32, 1 bf16 (element type of every layer's wp / wrp) */
-  const float* x;       /* [B][3][V] */
+  int F;                /* input features per joint; 0 = 3 */
+  const float* x;       /* [B][F][V] */
   const int* active;    /* [B] */
-  const float* ln_w;    /* [3*V] */
+  const float* ln_w;    /* [F*V] */
   const float* ln_b;
-  const float* w_in;    /* [C0][3] */
+  const float* w_in;    /* [C0][F] */
   const float* b_in;    /* [C0] */
   const float* w_out;   /* [K][C_last] */
   const float* b_out;   /* [K] or NULL */
@@ -607,7 +618,7 @@ int stgcn_co_finish(const stgcn_co_layer* d, void* stream);
 
 /* CoST-GCN per-frame inference for B independent streams (co_streams.hip): one call advances every active stream by one
  * frame through the whole network.  Per stream the arithmetic is stgcn_co_layer's four stages (gcn, push, taps,
- * finish) between an input head (LayerNorm([3,1,V]) + fcn_in) and an output head (mean over V + fcn_out); every
+ * finish) between an input head (LayerNorm([F,1,V]) + fcn_in) and an output head (mean over V + fcn_out); every
  * hand-off is a kernel boundary, no atomics on floating-point data, no cooperative launch.
  * State is stream-major and updated in place: ring [B][fifo][V][Cout] (dtype elements, fifo = S*(Kt-1)+1), res_ring
  * [B][Kt/2+1][V][Cout] fp32, idx [B][2].  active [B] (device int32, read by the kernels): 0 = skip (the stream's state
@@ -648,11 +659,12 @@ typedef struct {
 } stgcn_co_streams_layer;
 typedef struct {
   int B, V, L, C0, K, dtype;
-  const float* x;       /* [B][3][V] */
+  int F;                /* input features per joint; 0 = 3 */
+  const float* x;       /* [B][F][V] */
   const int* active;    /* [B] */
-  const float* ln_w;    /* [3*V] */
+  const float* ln_w;    /* [F*V] */
   const float* ln_b;
-  const float* w_in;    /* [C0][3] */
+  const float* w_in;    /* [C0][F] */
   const float* b_in;    /* [C0] */
   const float* w_out;   /* [K][C_last] */
   const float* b_out;   /* [K] or NULL */
@@ -677,7 +689,7 @@ int stgcn_co_streams(const stgcn_co_streams_desc* d, void* stream);
  * is.  The stages, the order of every sum and the split count (stgcn_co_clip_splits) are described there.  Hence
  * chunk invariance: a clip of T frames and any split of it into consecutive clips (T = 1 included) give the same bits
  * in out, ring, res_ring and idx; a captured graph of a clip replays bit-identically.
- * x: the (3, T, V) fp32 clip, channel c of frame t at x[c * x_stride + t * V] (x_stride >= T * V: a dense clip has
+ * x: the (F, T, V) fp32 clip, channel c of frame t at x[c * x_stride + t * V] (x_stride >= T * V: a dense clip has
  * x_stride = T * V, a chunk of a longer clip keeps the whole clip's stride).  out: [T][K].
  * wt: stgcn_co_pack_weight's image; wp / wrp: stgcn_rt_streams_pack_weight's (groups = P / 1), fp32.
  * dtype 0 fp32 | 1 bf16: the element type of wt, ring and hist only.
@@ -716,11 +728,12 @@ typedef struct {
 typedef stgcn_co_clip_layer stgcn_co_streams_clip_layer;
 typedef struct {
   int T, V, L, C0, K, dtype;
+  int F;                /* input features per joint; 0 = 3 */
   long x_stride;        /* elements between two channels of x */
   const float* x;       /* the clip, see above */
-  const float* ln_w;    /* [3*V] */
+  const float* ln_w;    /* [F*V] */
   const float* ln_b;
-  const float* w_in;    /* [C0][3] */
+  const float* w_in;    /* [C0][F] */
   const float* b_in;    /* [C0] */
   const float* w_out;   /* [K][C_last] */
   const float* b_out;   /* [K] or NULL */
@@ -773,15 +786,16 @@ int stgcn_co_clip(const stgcn_co_clip_desc* d, void* stream);
  * returns 1 (2 for the dtype) before any launch; the two queries return -1. */
 typedef struct {
   int B, T, t0, V, L, C0, K, dtype;
+  int F;                /* input features per joint; 0 = 3 */
   long x_stride;        /* elements between two channels of x */
   long x_bstride;       /* elements between two streams of x */
   long out_bstride;     /* elements between two streams of out */
   const float* x;       /* this call's first frame of stream 0, see above */
   const int* active;    /* [B] */
   const int* lengths;   /* [B] */
-  const float* ln_w;    /* [3*V] */
+  const float* ln_w;    /* [F*V] */
   const float* ln_b;
-  const float* w_in;    /* [C0][3] */
+  const float* w_in;    /* [C0][F] */
   const float* b_in;    /* [C0] */
   const float* w_out;   /* [K][C_last] */
   const float* b_out;   /* [K] or NULL */
@@ -822,6 +836,7 @@ int stgcn_co_streams_clip(const stgcn_co_streams_clip_desc* d, void* stream);
 #define STGCN_RT_CLIP_MAX_T 256
 typedef struct {
   int B, T, t0, V, L, C0, K, dtype;
+  int F;                /* input features per joint; 0 = 3 */
   long x_stride;        /* elements between two channels of x */
   long x_bstride;       /* elements between two streams of x */
   long out_bstride;     /* elements between two streams of out */
@@ -829,9 +844,9 @@ typedef struct {
   const float* x;       /* this call's first frame of stream 0, see above */
   const int* active;    /* [B] */
   const int* lengths;   /* [B] */
-  const float* ln_w;    /* [3*V] */
+  const float* ln_w;    /* [F*V] */
   const float* ln_b;
-  const float* w_in;    /* [C0][3] */
+  const float* w_in;    /* [C0][F] */
   const float* b_in;    /* [C0] */
   const float* w_out;   /* [K][C_last] */
   const float* b_out;   /* [K] or NULL */

@@ -87,6 +87,7 @@ class PrepJob(ctypes.Structure):
 
 
 RT_MAX_LAYERS = 12  # STGCN_RT_MAX_LAYERS
+MAX_IN_FEAT = 16  # STGCN_MAX_IN_FEAT: the descriptors' F (in_feat of the input head); 0 reads as 3
 
 
 class RtLayer(ctypes.Structure):
@@ -96,7 +97,7 @@ class RtLayer(ctypes.Structure):
 
 
 class RtFrameDesc(ctypes.Structure):
-    _fields_ = [(n, c_int) for n in ("V", "L", "C0", "K", "blocks")] + \
+    _fields_ = [(n, c_int) for n in ("V", "L", "C0", "K", "blocks", "F")] + \
                [(n, c_void_p) for n in ("x", "ln_w", "ln_b", "w_in", "b_in", "w_out", "b_out", "out", "sync",
                                         "status")] + \
                [("layers", RtLayer * RT_MAX_LAYERS)]
@@ -109,7 +110,7 @@ class RtStreamsLayer(ctypes.Structure):  # stgcn_rt_streams_layer
 
 
 class RtStreamsDesc(ctypes.Structure):  # stgcn_rt_streams_desc
-    _fields_ = [(n, c_int) for n in ("V", "L", "C0", "K", "B", "dtype")] + \
+    _fields_ = [(n, c_int) for n in ("V", "L", "C0", "K", "B", "dtype", "F")] + \
                [(n, c_void_p) for n in ("x", "active", "ln_w", "ln_b", "w_in", "b_in", "w_out", "b_out", "out")] + \
                [("layers", RtStreamsLayer * RT_MAX_LAYERS)]
 
@@ -129,7 +130,7 @@ class CoStreamsLayer(ctypes.Structure):  # stgcn_co_streams_layer
 
 
 class CoStreamsDesc(ctypes.Structure):  # stgcn_co_streams_desc
-    _fields_ = [(n, c_int) for n in ("B", "V", "L", "C0", "K", "dtype")] + \
+    _fields_ = [(n, c_int) for n in ("B", "V", "L", "C0", "K", "dtype", "F")] + \
                [(n, c_void_p) for n in ("x", "active", "ln_w", "ln_b", "w_in", "b_in", "w_out", "b_out", "h0", "order",
                                         "out")] + \
                [("layers", CoStreamsLayer * RT_MAX_LAYERS)]
@@ -146,7 +147,7 @@ class CoClipLayer(ctypes.Structure):  # stgcn_co_clip_layer
 
 
 class CoClipDesc(ctypes.Structure):  # stgcn_co_clip_desc
-    _fields_ = [(n, c_int) for n in ("T", "V", "L", "C0", "K", "dtype")] + [("x_stride", c_long)] + \
+    _fields_ = [(n, c_int) for n in ("T", "V", "L", "C0", "K", "dtype", "F")] + [("x_stride", c_long)] + \
                [(n, c_void_p) for n in ("x", "ln_w", "ln_b", "w_in", "b_in", "w_out", "b_out", "h0", "out")] + \
                [("layers", CoClipLayer * RT_MAX_LAYERS)]
 
@@ -156,7 +157,7 @@ class CoStreamsClipLayer(ctypes.Structure):  # stgcn_co_streams_clip_layer
 
 
 class CoStreamsClipDesc(ctypes.Structure):  # stgcn_co_streams_clip_desc
-    _fields_ = [(n, c_int) for n in ("B", "T", "t0", "V", "L", "C0", "K", "dtype")] + \
+    _fields_ = [(n, c_int) for n in ("B", "T", "t0", "V", "L", "C0", "K", "dtype", "F")] + \
                [(n, c_long) for n in ("x_stride", "x_bstride", "out_bstride")] + \
                [(n, c_void_p) for n in ("x", "active", "lengths", "ln_w", "ln_b", "w_in", "b_in", "w_out", "b_out",
                                         "h0", "out")] + \
@@ -167,7 +168,7 @@ RT_CLIP_MAX_T = 256  # STGCN_RT_CLIP_MAX_T
 
 
 class RtStreamsClipDesc(ctypes.Structure):  # stgcn_rt_streams_clip_desc
-    _fields_ = [(n, c_int) for n in ("B", "T", "t0", "V", "L", "C0", "K", "dtype")] + \
+    _fields_ = [(n, c_int) for n in ("B", "T", "t0", "V", "L", "C0", "K", "dtype", "F")] + \
                [(n, c_long) for n in ("x_stride", "x_bstride", "out_bstride", "fstride")] + \
                [(n, c_void_p) for n in ("x", "active", "lengths", "ln_w", "ln_b", "w_in", "b_in", "w_out", "b_out",
                                         "xb", "z", "r", "a", "out")] + \
@@ -273,6 +274,8 @@ _SIGS = {
                                c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "stgcn_layer_fused_fwd": (c_int, [ctypes.POINTER(LayerFusedDesc), c_void_p]),
     "stgcn_rt_frame_in": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "stgcn_rt_frame_in_f": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                    c_void_p]),
     "stgcn_rt_frame_gcn": (c_int, [c_void_p, c_int, c_int, c_int, c_int] + [c_void_p] * 10),
     "stgcn_rt_frame_norm": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                     c_void_p, c_int, c_int, c_void_p, c_void_p]),

@@ -15,7 +15,7 @@ the weight packs) are rebuilt whenever parameters may have changed — ``load_st
 restarts the stream.  ``reset_state()`` restarts it explicitly and keeps the buffers (a captured graph stays valid).
 
 Scope: LayerNorm only (the reference's BatchNorm variant takes statistics over whatever the FIFO holds), batch 1,
-inference only, in_feat 3, V <= 32, P <= 3, channels % 4 == 0 and <= 256, odd Kt <= 69, stride 1 or 2.
+inference only, 1 <= in_feat <= 16, V <= 32, P <= 3, channels % 4 == 0 and <= 256, odd Kt <= 69, stride 1 or 2.
 
 ``forward_clip(x (1, in_feat, T, V)) -> (1, num_classes, T)`` advances the same stream by T frames in one call
 (stgcn_co_clip): every layer's temporal conv becomes one GEMM with T*V rows that reads the tap weights once per clip.
@@ -73,6 +73,13 @@ class CoStgcnLayer(nn.Module):
 def empty_ring_row(l, V):
     """An empty FIFO as the activation ring caches it: ReLU(LN1(0)) = ReLU(tcn.0.bias), rows [V][C] fp32."""
     return torch.relu(l.tcn[0].bias.detach().float()).reshape(l.out_channels, V).t()
+
+
+def _check_in_feat(model):
+    F = model.fcn_in.in_channels
+    if not 1 <= F <= K.L.MAX_IN_FEAT or model.norm_in.weight.shape[0] != F:
+        raise RuntimeError(f"stgcn_amd: co-st-gcn per-frame input head takes 1 <= in_feat <= {K.L.MAX_IN_FEAT}, got "
+                           f"{F}")
 
 
 def _fill_layer(y, l, A_eff, keep, dt):
@@ -199,8 +206,7 @@ class Model(nn.Module):
         V, P = self.A.shape[-1], self.A.shape[0]
         if len(self.gcn_networks) > K.L.RT_MAX_LAYERS:
             raise RuntimeError(f"stgcn_amd: co-st-gcn supports at most {K.L.RT_MAX_LAYERS} layers")
-        if self.fcn_in.in_channels != 3 or self.norm_in.weight.shape[0] != 3:
-            raise RuntimeError("stgcn_amd: co-st-gcn per-frame input head takes in_feat == 3")
+        _check_in_feat(self)
         p = keep = Keep()
         descs, state = [], []
         for i, l in enumerate(self.gcn_networks):
@@ -373,8 +379,7 @@ class CoStreamBatch(StreamBatch):
 
     def __init__(self, model, B, splits=0):
         super().__init__(model, B)
-        if model.fcn_in.in_channels != 3 or model.norm_in.weight.shape[0] != 3:
-            raise RuntimeError("stgcn_amd: co-st-gcn per-frame input head takes in_feat == 3")
+        _check_in_feat(model)
         if len(model.gcn_networks) > K.L.RT_MAX_LAYERS:
             raise RuntimeError(f"stgcn_amd: co-st-gcn supports at most {K.L.RT_MAX_LAYERS} layers")
         self.splits, self._scratch, self._dtype = int(splits), None, None
@@ -461,7 +466,7 @@ class CoStreamBatch(StreamBatch):
         d0, _ = self._desc()
         m = self.model
         d = K.L.CoStreamsClipDesc()
-        d.B, d.T, d.V, d.L, d.C0, d.K, d.dtype = self.B, cap, self.V, d0.L, d0.C0, d0.K, d0.dtype
+        d.B, d.T, d.V, d.L, d.C0, d.K, d.dtype, d.F = self.B, cap, self.V, d0.L, d0.C0, d0.K, d0.dtype, d0.F
         for n in ("ln_w", "ln_b", "w_in", "b_in", "w_out", "b_out"):
             setattr(d, n, getattr(d0, n))
         for y, c in zip(d.layers, d0.layers):

@@ -306,7 +306,11 @@ int stgcn_layer_fused_fwd(const stgcn_layer_fused_desc* d, void* stream) {
 
 int stgcn_rt_frame_in(const float* x, int V, const float* ln_w, const float* ln_b, const float* w, const float* b, int C0,
                       float* out, void* stream) {
-  return rt_in_launch(x, V, ln_w, ln_b, w, b, C0, out, STREAM(stream));
+  return stgcn_rt_frame_in_f(x, 3, V, ln_w, ln_b, w, b, C0, out, stream);
+}
+int stgcn_rt_frame_in_f(const float* x, int F, int V, const float* ln_w, const float* ln_b, const float* w, const float* b,
+                        int C0, float* out, void* stream) {
+  return rt_in_launch(x, V, ln_w, ln_b, w, b, C0, out, F, STREAM(stream));
 }
 int stgcn_rt_frame_gcn(const float* x, int V, int Cin, int Cout, int P, const float* A, const float* w, const float* bias2d,
                        float* fifo, float* acc, const int* idx, const float* wr, float* a_out, float* r_out,

@@ -36,16 +36,16 @@ inline int num_splits(int Cout, int Kt, int forced) {
 }
 
 // ---------------------------------------------------------------------------------------------------- heads
-// x: channel c of the frame at x[c * x_stride + v]; xf / xi: 3 * VMAX floats of LDS each, red: HNT / 64
-DEV void in_frame(const float* __restrict__ x, long x_stride, int V, int C0, const float* __restrict__ ln_w,
+// x: channel c of the frame at x[c * x_stride + v]; xf / xi: F * V floats of LDS each, red: HNT / 64
+DEV void in_frame(const float* __restrict__ x, long x_stride, int F, int V, int C0, const float* __restrict__ ln_w,
                   const float* __restrict__ ln_b, const float* __restrict__ w_in, const float* __restrict__ b_in,
                   float* xf, float* xi, float* red, float* __restrict__ h0) {
-  for (int i = threadIdx.x; i < 3 * V; i += HNT) {
+  for (int i = threadIdx.x; i < F * V; i += HNT) {
     const int c = i / V, v = i - c * V;
     xf[i] = x[c * x_stride + v];
   }
   __syncthreads();
-  frame_head_in<HNT>(xf, V, C0, ln_w, ln_b, w_in, b_in, xi, red, h0, C0);
+  frame_head_in<HNT>(xf, F, V, C0, ln_w, ln_b, w_in, b_in, xi, red, h0, C0);
 }
 
 // ---------------------------------------------------------------------------------------------------- gcn

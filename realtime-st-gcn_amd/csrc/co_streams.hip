@@ -4,7 +4,7 @@
 // then step, anything else step).  One tick = these launches on one stream, every hand-off a kernel boundary:
 //
 //   cs_order  : order[0] = number of active streams, order[1..] = their slots (the tap stage's groups)       (1 block)
-//   cs_in     : h0[b] = fcn_in(LayerNorm([3,1,V])(x[b])): frame_head_in                           (1 block per stream)
+//   cs_in     : h0[b] = fcn_in(LayerNorm([F,1,V])(x[b])): frame_head_in                           (1 block per stream)
 //   per layer:
 //   cs_gcn    : z[b] = gcn(x[b], A), r[b] = Wr x[b] + br.  One block per stream, x[b] in LDS; a wave owns a 32-channel
 //               tile: per partition p, Y_p = x W_p^T on v_mfma_f32_32x32x2_f32 with the packed weight image (the B
@@ -60,15 +60,15 @@ __global__ __launch_bounds__(HNT) void cs_order_kernel(const int* __restrict__ a
 }
 
 // frame_head_in of one stream's frame -> h0[b] rows [V][C0]
-__global__ __launch_bounds__(HNT) void cs_in_kernel(const float* __restrict__ x, const int* __restrict__ active, int V,
-                                                    int C0, const float* __restrict__ ln_w,
+__global__ __launch_bounds__(HNT) void cs_in_kernel(const float* __restrict__ x, const int* __restrict__ active, int F,
+                                                    int V, int C0, const float* __restrict__ ln_w,
                                                     const float* __restrict__ ln_b, const float* __restrict__ w_in,
                                                     const float* __restrict__ b_in, float* __restrict__ h0) {
-  __shared__ float xi[3 * VMAX];
+  __shared__ float xi[FMAX * VMAX];
   __shared__ float red[HNT / 64];
   const long b = blockIdx.x;
   if (active[b] == 0) return;
-  frame_head_in<HNT>(x + b * 3 * V, V, C0, ln_w, ln_b, w_in, b_in, xi, red, h0 + b * V * C0, C0);
+  frame_head_in<HNT>(x + b * F * V, F, V, C0, ln_w, ln_b, w_in, b_in, xi, red, h0 + b * V * C0, C0);
 }
 
 // frame_head_out of one stream's last rows; a zero row for a skipped stream
@@ -268,7 +268,8 @@ void launch_taps(const layer_t& y, int V, int nks, int nsplit, const int* order,
 
 // 0 when the descriptor's shapes, dtype and (unless shapes_only) pointers are usable
 int co_streams_check(const stgcn_co_streams_desc& d, bool shapes_only) {
-  if (d.B < 1 || d.L < 1 || d.L > STGCN_RT_MAX_LAYERS || d.K < 1 || d.C0 < 4 || d.C0 > CMAX || d.C0 % 4)
+  if (d.B < 1 || d.L < 1 || d.L > STGCN_RT_MAX_LAYERS || d.K < 1 || d.C0 < 4 || d.C0 > CMAX || d.C0 % 4 ||
+      !head_feats_ok(d.F, d.V))
     return STGCN_EBADSHAPE;
   int cin = d.C0;
   for (int l = 0; l < d.L; ++l) {
@@ -309,7 +310,7 @@ int co_streams_num_splits(const stgcn_co_streams_desc& d, int l) {
 int co_streams_launch(const stgcn_co_streams_desc& d, hipStream_t s) {
   const int B = d.B, V = d.V;
   hipLaunchKernelGGL(cs_order_kernel, dim3(1), dim3(HNT), 0, s, d.active, B, d.order);
-  hipLaunchKernelGGL(cs_in_kernel, dim3((unsigned)B), dim3(HNT), 0, s, d.x, d.active, V, d.C0, d.ln_w, d.ln_b, d.w_in,
+  hipLaunchKernelGGL(cs_in_kernel, dim3((unsigned)B), dim3(HNT), 0, s, d.x, d.active, head_feats(d.F), V, d.C0, d.ln_w, d.ln_b, d.w_in,
                      d.b_in, d.h0);
   const float* x = d.h0;
   for (int l = 0; l < d.L; ++l) {

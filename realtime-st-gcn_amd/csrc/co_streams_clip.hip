@@ -20,7 +20,7 @@
 //
 // Launches per call, 2 + 5 L whatever B and T are, every hand-off a kernel boundary, no workgroup waits on another;
 // blockIdx.x = b * (blocks per stream) + i:
-//   csc_in     : T blocks per stream: h0[b][t] = fcn_in(LayerNorm([3,1,V])(x[b][:, t])): frame_head_in          (i < n_b)
+//   csc_in     : T blocks per stream: h0[b][t] = fcn_in(LayerNorm([F,1,V])(x[b][:, t])): frame_head_in          (i < n_b)
 //   per layer:
 //   csc_gcn    : T per stream: z[b][t] = gcn(x[t], A), r[b][t] = Wr x[t] + br: cs_gcn_kernel's body            (i < n_b)
 //   csc_push   : T + fifo-1 + Kt/2 per stream: co_push_stage of frame i into hist[b][fifo-1+i] / resq[b][Kt/2+i]
@@ -83,18 +83,18 @@ DEV int stream_frames(const Call c, long b, bool& restart) {
 }
 
 // ---------------------------------------------------------------------------------------------------- heads
-// x is the (3, T, V) clip of stream b as given: channel c of frame t at x[b * x_bstride + c * x_stride + t * V]
+// x is the (F, T, V) clip of stream b as given: channel c of frame t at x[b * x_bstride + c * x_stride + t * V]
 __global__ __launch_bounds__(HNT) void csc_in_kernel(const Call c, const float* __restrict__ x, long x_stride,
-                                                     long x_bstride, int V, int C0, const float* __restrict__ ln_w,
+                                                     long x_bstride, int F, int V, int C0, const float* __restrict__ ln_w,
                                                      const float* __restrict__ ln_b, const float* __restrict__ w_in,
                                                      const float* __restrict__ b_in, float* __restrict__ h0) {
-  __shared__ float xf[3 * VMAX];
-  __shared__ float xi[3 * VMAX];
+  __shared__ float xf[FMAX * VMAX];
+  __shared__ float xi[FMAX * VMAX];
   __shared__ float red[HNT / 64];
   const long b = blockIdx.x / c.T, t = blockIdx.x - b * c.T;
   bool restart;
   if (t >= stream_frames(c, b, restart)) return;
-  in_frame(x + b * x_bstride + t * V, x_stride, V, C0, ln_w, ln_b, w_in, b_in, xf, xi, red, h0 + (b * c.T + t) * V * C0);
+  in_frame(x + b * x_bstride + t * V, x_stride, F, V, C0, ln_w, ln_b, w_in, b_in, xf, xi, red, h0 + (b * c.T + t) * V * C0);
 }
 
 __global__ __launch_bounds__(HNT) void csc_out_kernel(const Call c, const float* __restrict__ y, int V, int C,
@@ -206,7 +206,7 @@ void launch_layer(const layer_t& y, const Call& c, int B, int V, int nsplit, con
 template <typename D>
 int check_shapes(const D& d) {
   if (d.T < 1 || d.T > STGCN_CO_CLIP_MAX_T || d.L < 1 || d.L > STGCN_RT_MAX_LAYERS || d.K < 1 || d.C0 < 4 ||
-      d.C0 > CMAX || d.C0 % 4)
+      d.C0 > CMAX || d.C0 % 4 || !head_feats_ok(d.F, d.V))
     return STGCN_EBADSHAPE;
   int cin = d.C0;
   for (int l = 0; l < d.L; ++l) {
@@ -240,7 +240,8 @@ template <typename D>
 int launch(const D& d, const Call& c, int B, long x_bstride, long out_bstride, hipStream_t s) {
   const int V = d.V;
   const unsigned nbt = (unsigned)B * (unsigned)d.T;
-  hipLaunchKernelGGL(csc_in_kernel, dim3(nbt), dim3(HNT), 0, s, c, d.x, d.x_stride, x_bstride, V, d.C0, d.ln_w, d.ln_b,
+  hipLaunchKernelGGL(csc_in_kernel, dim3(nbt), dim3(HNT), 0, s, c, d.x, d.x_stride, x_bstride, head_feats(d.F), V, d.C0, d.ln_w,
+                     d.ln_b,
                      d.w_in, d.b_in, d.h0);
   const float* x = d.h0;
   for (int l = 0; l < d.L; ++l) {
@@ -285,7 +286,7 @@ int co_streams_clip_check(const stgcn_co_streams_clip_desc& d, bool shapes_only)
   if (rc != STGCN_OK) return rc;
   if ((long)d.B * max_blocks_per_stream(d) > 0x7fffffffL) return STGCN_EBADSHAPE;  // blockIdx.x carries (stream, block)
   if (shapes_only) return STGCN_OK;
-  if (!d.active || !d.lengths || d.out_bstride < (long)d.T * d.K || (d.B > 1 && d.x_bstride < 3 * d.x_stride))
+  if (!d.active || !d.lengths || d.out_bstride < (long)d.T * d.K || (d.B > 1 && d.x_bstride < head_feats(d.F) * d.x_stride))
     return STGCN_EBADSHAPE;
   return check_pointers(d);
 }

@@ -27,6 +27,7 @@
 constexpr int VMAX = 32;    // joints: the 32-row MFMA operand
 constexpr int CMAX = 256;   // channels per layer
 constexpr int PMAX = 3;     // graph partitions
+constexpr int FMAX = 16;    // input features per joint (the input head's in_feat)
 constexpr int KTMAX = 69;   // temporal taps (co-st-gcn)
 constexpr int MAXE = 7680;  // V * C of the routes that keep a frame in one workgroup's LDS / registers
 constexpr int XPAD = 4;     // LDS row stride = C + XPAD floats: the 32 rows of a fragment read spread over the banks
@@ -179,13 +180,31 @@ DEV typename Tr<T>::frag load_a_as(const float* xs, int ld, int ks, int nks, int
 }
 
 // ------------------------------------------------------------------------------------------- heads
-// Input head: LayerNorm([3,1,V]) (per frame, two-pass, unbiased variance) + fcn_in (1x1 conv + bias) of the frame x
-// (element c*V + v) -> rows out[v * ld + co].  xi: 3 * V floats of LDS, red: NTH / 64.  No trailing barrier.
+// The descriptors' F field: 0 (a descriptor filled before the field existed) reads as 3
+__host__ __device__ inline int head_feats(int F) { return F == 0 ? 3 : F; }
+// F as given in a descriptor is usable: 0 or 1 .. FMAX, and the unbiased variance over F * V values exists
+inline bool head_feats_ok(int F, int V) { return F >= 0 && F <= FMAX && head_feats(F) * V >= 2; }
+
+// fcn_in of one output: b + sum over c < F of w[c] * xn[c * V], the fmaf chain in ascending c from the bias.  FC > 0
+// is F at compile time (the chain unrolled); both forms give the same bits.
+template <int FC>
+DEV float head_dot(const float* __restrict__ w, const float* xn, int F, int V, float b) {
+  if constexpr (FC > 0) {
+#pragma unroll
+    for (int c = 0; c < FC; ++c) b = fmaf(w[c], xn[c * V], b);
+  } else {
+    for (int c = 0; c < F; ++c) b = fmaf(w[c], xn[c * V], b);
+  }
+  return b;
+}
+
+// Input head: LayerNorm([F,1,V]) (per frame, two-pass, unbiased variance) + fcn_in (1x1 conv + bias) of the frame x
+// (element c*V + v) -> rows out[v * ld + co].  xi: F * V floats of LDS, red: NTH / 64.  No trailing barrier.
 template <int NTH>
-DEV void frame_head_in(const float* __restrict__ x, int V, int C0, const float* __restrict__ ln_w,
+DEV void frame_head_in(const float* __restrict__ x, int F, int V, int C0, const float* __restrict__ ln_w,
                        const float* __restrict__ ln_b, const float* __restrict__ w_in, const float* __restrict__ b_in,
                        float* xi, float* red, float* out, int ld) {
-  const int tid = threadIdx.x, n = 3 * V;
+  const int tid = threadIdx.x, n = F * V;
   for (int i = tid; i < n; i += NTH) xi[i] = x[i];
   __syncthreads();
   float s = 0.f;
@@ -200,12 +219,18 @@ DEV void frame_head_in(const float* __restrict__ x, int V, int C0, const float* 
   __syncthreads();
   for (int i = tid; i < n; i += NTH) xi[i] = fmaf(ln_w[i], (xi[i] - mean) * rstd, ln_b[i]);
   __syncthreads();
-  for (int i = tid; i < V * C0; i += NTH) {
-    const int v = i / C0, co = i - v * C0;
-    float t = b_in[co];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) t = fmaf(w_in[co * 3 + c], xi[c * V + v], t);
-    out[v * ld + co] = t;
+  // F == 3 (skeleton coordinates) keeps the unrolled chain it had before F became a runtime value: with the runtime
+  // loop alone the bf16 stream-batch tick measured 1.4 - 1.6 % slower
+  if (F == 3) {
+    for (int i = tid; i < V * C0; i += NTH) {
+      const int v = i / C0, co = i - v * C0;
+      out[v * ld + co] = head_dot<3>(w_in + co * 3, xi + v, 3, V, b_in[co]);
+    }
+  } else {
+    for (int i = tid; i < V * C0; i += NTH) {
+      const int v = i / C0, co = i - v * C0;
+      out[v * ld + co] = head_dot<0>(w_in + co * F, xi + v, F, V, b_in[co]);
+    }
   }
 }
 

@@ -107,7 +107,7 @@ int attn_bwd_launch(const void* th, const void* ph, int ld, int N, int T_, int V
 int layer_fused_launch(const stgcn_layer_fused_desc& a, hipStream_t s);
 // rt_fused.hip
 int rt_in_launch(const float* x, int V, const float* g, const float* b, const float* W, const float* bias, int C0,
-                 float* out, hipStream_t s);
+                 float* out, int F, hipStream_t s);
 int rt_gcn_launch(const float* x, int V, int Cin, int Cout, int P, const float* A, const float* W, const float* bias2d,
                   float* fifo, float* acc, const int* idx, const float* Wr, float* a_out, float* r_out,
                   hipStream_t s);

@@ -3,7 +3,7 @@
 // per layer + 1 for the input head + 1 for the output head (the eager op-by-op path took ~60 launches and
 // ~1 ms per frame, most of it tile-GEMM kernels sized for batches running a 25-row GEMM).
 //
-//   rt_in     : x (1,3,1,V) -> LayerNorm([3,1,V]) (per frame, unbiased var; layernorm.py:22-28) -> fcn_in
+//   rt_in     : x (1,F,1,V) -> LayerNorm([F,1,V]) (per frame, unbiased var; layernorm.py:22-28) -> fcn_in
 //               (1x1 conv + bias; rtstgcn.py:103) -> rows [V][C0]: frame_head_in                  (1 block)
 //   rt_gcn    : z = conv1x1(x) (+bias) mixed by A (tgcn as the online layer applies it, rtstgcn.py:531-537)
 //               evaluated as z[v][co] = bias2d[v][co] + sum_{p,ci} W[p*Cout+co][ci] * XA_p[v][ci],
@@ -43,10 +43,11 @@ DEV float2 ln_stats(const float* x, int n, float eps, float* red) {
 
 __global__ __launch_bounds__(NT) void rt_in_kernel(const float* __restrict__ x, int V, const float* __restrict__ g,
                                                    const float* __restrict__ b, const float* __restrict__ W,
-                                                   const float* __restrict__ bias, int C0, float* __restrict__ out) {
-  __shared__ float xs[3 * VMAX];
+                                                   const float* __restrict__ bias, int C0, float* __restrict__ out,
+                                                   int F) {
+  __shared__ float xs[FMAX * VMAX];
   __shared__ float red[NT / 64];
-  frame_head_in<NT>(x, V, C0, g, b, W, bias, xs, red, out, C0);
+  frame_head_in<NT>(x, F, V, C0, g, b, W, bias, xs, red, out, C0);
 }
 
 // conv first, as the reference (tgcn: conv1x1 then @A): y_p[u][co] = W_p[co] . x[u] for the block's GCN_CB
@@ -390,9 +391,9 @@ DEV float4 ld_wt4(__amdgpu_buffer_rsrc_t r, int e4) {
   return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r, e4 * 16, 0, 16));
 }
 
-// dynamic LDS carve (floats): xs [VMAX*CMAX] (the current layer's input), wsm, ys, As, red, idx
+// dynamic LDS carve (floats): xs [VMAX*CMAX] (the current layer's input), wsm, ys, As, red, idx, xi
 constexpr int RF_LDS_FLOATS = VMAX * CMAX + RF_WROWS * CMAX + PMAX * VMAX * RF_CB + PMAX * VMAX * VMAX + 64 +
-                              2 * STGCN_RT_MAX_LAYERS;
+                              2 * STGCN_RT_MAX_LAYERS + FMAX * VMAX;
 
 __global__ __launch_bounds__(RF_NT) void rt_frame_kernel(const stgcn_rt_frame_desc d) {
   extern __shared__ __attribute__((aligned(16))) float rf_sm[];
@@ -410,10 +411,10 @@ __global__ __launch_bounds__(RF_NT) void rt_frame_kernel(const stgcn_rt_frame_de
   if ((int)blockIdx.x * RF_CB < d.layers[0].Cout) rf_prefetch(d.layers[0], blockIdx.x * RF_CB, V, sidx[0], sidx[1], true, pre);
   else rf_prefetch(d.layers[0], 0, V, sidx[0], sidx[1], true, pre);  // A only is used
 
-  // input head: LayerNorm([3,1,V]) + fcn_in (rt_in_kernel's arithmetic), every workgroup
+  // input head: LayerNorm([F,1,V]) + fcn_in (rt_in_kernel's arithmetic), every workgroup
   {
-    float* xi = ys;  // 3 * V <= 96 < PMAX * VMAX * RF_CB
-    const int n = 3 * V;
+    float* xi = reinterpret_cast<float*>(sidx + 2 * STGCN_RT_MAX_LAYERS);  // [F][V]: wsm / As are staged under the head
+    const int F = head_feats(d.F), n = F * V;
     for (int i = tid; i < n; i += RF_NT) xi[i] = d.x[i];
     __syncthreads();
     const float2 st = ln_stats(xi, n, 1e-5f, red);
@@ -422,10 +423,8 @@ __global__ __launch_bounds__(RF_NT) void rt_frame_kernel(const stgcn_rt_frame_de
     __syncthreads();
     for (int i = tid; i < V * d.C0; i += RF_NT) {
       const int v = i / d.C0, co = i - v * d.C0;
-      float s = d.b_in[co];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) s = fmaf(d.w_in[co * 3 + c], xi[c * V + v], s);
-      xs[i] = s;
+      xs[i] = F == 3 ? head_dot<3>(d.w_in + co * 3, xi + v, 3, V, d.b_in[co])
+                     : head_dot<0>(d.w_in + co * F, xi + v, F, V, d.b_in[co]);
     }
   }
 
@@ -619,7 +618,7 @@ int rt_frame_launch(const stgcn_rt_frame_desc& d, hipStream_t s) {
   if (!d.x || !d.ln_w || !d.ln_b || !d.w_in || !d.b_in || !d.w_out || !d.out || !d.sync || !d.status)
     return STGCN_EBADSHAPE;
   if (d.V < 2 || d.V > VMAX || d.L < 1 || d.L > STGCN_RT_MAX_LAYERS || d.C0 < 4 || d.C0 > CMAX || d.C0 % 4 || d.K < 1 ||
-      d.blocks < 0 || d.blocks > 256)
+      d.blocks < 0 || d.blocks > 256 || !head_feats_ok(d.F, d.V))
     return STGCN_EBADSHAPE;
   int cin = d.C0;
   for (int l = 0; l < d.L; ++l) {
@@ -648,9 +647,9 @@ extern "C" int stgcn_rt_prof(void* dst, long n) {
 }
 
 int rt_in_launch(const float* x, int V, const float* g, const float* b, const float* W, const float* bias, int C0,
-                 float* out, hipStream_t s) {
-  if (!x || !g || !b || !W || !bias || !out || V < 2 || V > VMAX || C0 < 1) return STGCN_EBADSHAPE;
-  hipLaunchKernelGGL(rt_in_kernel, dim3(1), dim3(NT), 0, s, x, V, g, b, W, bias, C0, out);
+                 float* out, int F, hipStream_t s) {
+  if (!x || !g || !b || !W || !bias || !out || V < 2 || V > VMAX || C0 < 1 || F < 1 || F > FMAX) return STGCN_EBADSHAPE;
+  hipLaunchKernelGGL(rt_in_kernel, dim3(1), dim3(NT), 0, s, x, V, g, b, W, bias, C0, out, F);
   return hipGetLastError() == hipSuccess ? STGCN_OK : STGCN_EHIP;
 }
 

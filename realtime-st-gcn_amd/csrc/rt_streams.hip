@@ -62,7 +62,8 @@ __global__ __launch_bounds__(NT) void rt_streams_kernel(const stgcn_rt_streams_d
     }
   }
 
-  frame_head_in<NT>(d.x + b * 3 * V, V, d.C0, d.ln_w, d.ln_b, d.w_in, d.b_in, zs, red, xs, d.C0 + XPAD);
+  const int F = head_feats(d.F);
+  frame_head_in<NT>(d.x + b * F * V, F, V, d.C0, d.ln_w, d.ln_b, d.w_in, d.b_in, zs, red, xs, d.C0 + XPAD);
   __syncthreads();
 
   for (int l = 0; l < d.L; ++l) {
@@ -172,7 +173,7 @@ int launch_as(const stgcn_rt_streams_desc& d, hipStream_t s) {
 int rt_streams_launch(const stgcn_rt_streams_desc& d, hipStream_t s) {
   if (!d.x || !d.active || !d.ln_w || !d.ln_b || !d.w_in || !d.b_in || !d.w_out || !d.out) return STGCN_EBADSHAPE;
   if (d.V < 2 || d.V > VMAX || d.L < 1 || d.L > STGCN_RT_MAX_LAYERS || d.C0 < 4 || d.C0 > CMAX || d.C0 % 4 ||
-      d.V * d.C0 > MAXE || d.K < 1 || d.B < 1)
+      d.V * d.C0 > MAXE || d.K < 1 || d.B < 1 || !head_feats_ok(d.F, d.V))
     return STGCN_EBADSHAPE;
   if (d.dtype != 0 && d.dtype != 1) return STGCN_EDTYPE;
   int cin = d.C0;

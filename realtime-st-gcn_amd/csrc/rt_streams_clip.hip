@@ -84,14 +84,15 @@ __global__ __launch_bounds__(NT) void rtc_frame_kernel(const desc_t d, const int
   float* xb = d.xb + f;
 
   if (l == 0) {
-    float* xf = zs + 3 * VMAX;  // the frame [3][V], gathered from the clip's strides
+    const int F = head_feats(d.F);
+    float* xf = zs + F * VMAX;  // the frame [F][V], gathered from the clip's strides
     const float* x = d.x + b * d.x_bstride + (long)t * V;
-    for (int i = tid; i < 3 * V; i += NT) {
+    for (int i = tid; i < F * V; i += NT) {
       const int c = i / V;
       xf[i] = x[c * d.x_stride + (i - c * V)];
     }
     __syncthreads();
-    frame_head_in<NT>(xf, V, d.C0, d.ln_w, d.ln_b, d.w_in, d.b_in, zs, red, xs, d.C0 + XPAD);
+    frame_head_in<NT>(xf, F, V, d.C0, d.ln_w, d.ln_b, d.w_in, d.b_in, zs, red, xs, d.C0 + XPAD);
     __syncthreads();
     for (int i = tid; i < V * d.C0 / 4; i += NT) {
       const int v = i * 4 / d.C0, c = i * 4 - v * d.C0;
@@ -249,10 +250,12 @@ int max_e(const desc_t& d) {
 }
 
 // dynamic LDS of frame kernel l, from the network alone: xsf = its input rows, ef = its output rows (at least the
-// heads' scratch: 6 * VMAX floats of the input head, CMAX of the output head's pool, both within PMAX * ef)
+// heads' scratch: 2 * F * VMAX floats of the input head (frame kernel 0: up to 1024, more than three narrow output
+// rows hold), CMAX of the output head's pool, both within PMAX * ef)
 void frame_lds(const desc_t& d, int l, int& xsf, int& ef) {
   xsf = d.V * ((l == 0 ? d.C0 : d.layers[l - 1].Cout) + XPAD);
   ef = std::max(96, l < d.L ? d.V * d.layers[l].Cout : 0);
+  if (l == 0) ef = std::max(ef, ((2 * head_feats(d.F) * VMAX + PMAX - 1) / PMAX + 3) / 4 * 4);
 }
 
 template <typename T>
@@ -283,7 +286,8 @@ int rt_streams_clip_launch(const stgcn_rt_streams_clip_desc& d, hipStream_t s) {
   if (d.V < 2 || d.V > VMAX || d.L < 1 || d.L > STGCN_RT_MAX_LAYERS || d.C0 < 4 || d.C0 > CMAX || d.C0 % 4 ||
       d.V * d.C0 > MAXE || d.K < 1 || d.B < 1)
     return STGCN_EBADSHAPE;
-  if (d.T < 1 || d.T > STGCN_RT_CLIP_MAX_T || d.t0 < 0 || (long)d.B * d.T > 0x7fffffffL) return STGCN_EBADSHAPE;
+  if (d.T < 1 || d.T > STGCN_RT_CLIP_MAX_T || d.t0 < 0 || (long)d.B * d.T > 0x7fffffffL || !head_feats_ok(d.F, d.V))
+    return STGCN_EBADSHAPE;
   int cin = d.C0;
   bool resconv = false;
   for (int l = 0; l < d.L; ++l) {
@@ -300,7 +304,7 @@ int rt_streams_clip_launch(const stgcn_rt_streams_clip_desc& d, hipStream_t s) {
       !d.z || !d.a || (resconv && !d.r))
     return STGCN_EBADSHAPE;
   if (d.fstride < max_e(d) || d.fstride % 4 || d.x_stride < (long)d.T * d.V || d.out_bstride < (long)d.T * d.K ||
-      (d.B > 1 && d.x_bstride < 3 * d.x_stride))
+      (d.B > 1 && d.x_bstride < head_feats(d.F) * d.x_stride))
     return STGCN_EBADSHAPE;
   for (int l = 0; l < d.L; ++l) {
     const layer_t& y = d.layers[l];

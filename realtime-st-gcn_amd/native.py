@@ -959,13 +959,16 @@ def _f32c(t):
 
 
 def rt_frame_in(x, ln_w, ln_b, w, b):
-    """(1, 3, 1, V) frame -> LayerNorm([3,1,V]) -> fcn_in: rows (1, C0, 1, V) fp32."""
+    """(1, in_feat, 1, V) frame -> LayerNorm([in_feat,1,V]) -> fcn_in: rows (1, C0, 1, V) fp32."""
     L.require_device(x)
     x = _f32c(x)
-    V, C0 = x.shape[-1], w.shape[0]
+    F, V, C0 = x.shape[1], x.shape[-1], w.shape[0]
+    if w.shape[1] != F or ln_w.numel() != F * V or ln_b.numel() != F * V:
+        raise RuntimeError(f"stgcn_amd: rt_frame_in: x {tuple(x.shape)} does not match fcn_in {tuple(w.shape)} and a "
+                           f"LayerNorm of {ln_w.numel()} elements")
     out = cl_empty(1, C0, 1, V, torch.float32, x.device)
-    L.check(L.lib().stgcn_rt_frame_in(x.data_ptr(), V, _f32c(ln_w).data_ptr(), _f32c(ln_b).data_ptr(),
-                                      _f32c(w).data_ptr(), _f32c(b).data_ptr(), C0, out.data_ptr(), L.stream()),
+    L.check(L.lib().stgcn_rt_frame_in_f(x.data_ptr(), F, V, _f32c(ln_w).data_ptr(), _f32c(ln_b).data_ptr(),
+                                        _f32c(w).data_ptr(), _f32c(b).data_ptr(), C0, out.data_ptr(), L.stream()),
             "rt_frame_in")
     return out
 
@@ -1008,7 +1011,7 @@ def rt_frame_out(x, w, b):
 
 
 def rt_frame(desc, x, out):
-    """The whole RT per-frame step in one launch (stgcn_rt_frame): x (1, 3, 1, V) -> out (1, K, 1); ``desc`` is
+    """The whole RT per-frame step in one launch (stgcn_rt_frame): x (1, in_feat, 1, V) -> out (1, K, 1); ``desc`` is
     the model's stgcn_rt_frame_desc (rtstgcn.Model._build_frame_desc) with x / out filled in here."""
     L.require_device(x)
     x = _f32c(x)
@@ -1035,7 +1038,7 @@ def rt_streams_pack_weight(w, groups, dtype=torch.float32):
 
 
 def rt_streams(desc, x, active, out):
-    """One frame of every stream of a stream batch in one launch (stgcn_rt_streams): x (B, 3, 1, V) fp32 dense,
+    """One frame of every stream of a stream batch in one launch (stgcn_rt_streams): x (B, in_feat, 1, V) fp32 dense,
     active (B) int32, out (B, K, 1); ``desc`` is the batch's stgcn_rt_streams_desc (rtstgcn.RtStreamBatch)."""
     desc.x, desc.active, desc.out = x.data_ptr(), active.data_ptr(), out.data_ptr()
     L.check(L.lib().stgcn_rt_streams(ctypes.byref(desc), L.stream()), "rt_streams")
@@ -1094,7 +1097,7 @@ def co_streams_workspace(desc, layer):
 
 
 def co_streams(desc, x, active, out):
-    """One frame of every active stream of a CoST-GCN stream batch (stgcn_co_streams): x (B, 3, 1, V) fp32 dense,
+    """One frame of every active stream of a CoST-GCN stream batch (stgcn_co_streams): x (B, in_feat, 1, V) fp32 dense,
     active (B) int32, out (B, K, 1); ``desc`` is the batch's stgcn_co_streams_desc (costgcn.CoStreamBatch)."""
     desc.x, desc.active, desc.out = x.data_ptr(), active.data_ptr(), out.data_ptr()
     L.check(L.lib().stgcn_co_streams(ctypes.byref(desc), L.stream()), "co_streams")
@@ -1110,10 +1113,10 @@ def co_clip_workspace(desc, layer):
 
 
 def co_clip(desc, x, t0, T, out):
-    """Frames t0 .. t0+T-1 of the clip x (1, 3, T_all, V) fp32 dense through a CoST-GCN stream (stgcn_co_clip):
+    """Frames t0 .. t0+T-1 of the clip x (1, in_feat, T_all, V) fp32 dense through a CoST-GCN stream (stgcn_co_clip):
     rows t0 .. t0+T-1 of out (T_all, K); ``desc`` is the model's stgcn_co_clip_desc (costgcn.Model)."""
     V = x.shape[3]
-    desc.T, desc.x_stride = T, x.shape[2] * V
+    desc.F, desc.T, desc.x_stride = x.shape[1], T, x.shape[2] * V
     desc.x, desc.out = x.data_ptr() + 4 * t0 * V, out.data_ptr() + 4 * t0 * out.shape[1]
     L.check(L.lib().stgcn_co_clip(ctypes.byref(desc), L.stream()), "co_clip")
 
@@ -1128,12 +1131,12 @@ def co_streams_clip_workspace(desc, layer):
 
 
 def _streams_clip(name, desc, x, t0, T, active, lengths, out):
-    """Frames t0 .. t0+T-1 of the clips x (B, 3, T_all, V) fp32 dense through a stream batch's clip entry
+    """Frames t0 .. t0+T-1 of the clips x (B, in_feat, T_all, V) fp32 dense through a stream batch's clip entry
     ``stgcn_<name>``: stream b takes those below lengths[b]; rows t0 .. t0+T-1 of out (B, T_all, K).  active, lengths
     (B) int32 on the device; ``desc`` is the batch's clip descriptor."""
-    T_all, V = x.shape[2], x.shape[3]
-    desc.T, desc.t0 = T, t0
-    desc.x_stride, desc.x_bstride, desc.out_bstride = T_all * V, 3 * T_all * V, T_all * out.shape[2]
+    F, T_all, V = x.shape[1], x.shape[2], x.shape[3]
+    desc.F, desc.T, desc.t0 = F, T, t0
+    desc.x_stride, desc.x_bstride, desc.out_bstride = T_all * V, F * T_all * V, T_all * out.shape[2]
     desc.x, desc.out = x.data_ptr() + 4 * t0 * V, out.data_ptr() + 4 * t0 * out.shape[2]
     desc.active, desc.lengths = active.data_ptr(), lengths.data_ptr()
     L.check(getattr(L.lib(), "stgcn_" + name)(ctypes.byref(desc), L.stream()), name)

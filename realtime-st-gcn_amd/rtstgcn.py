@@ -249,7 +249,8 @@ class Model(nn.Module):
 
     def forward(self, x):
         if (self.online and self.normalization == "LayerNorm" and x.dim() == 4 and x.shape[0] == 1
-                and x.shape[2] == 1 and x.shape[1] == 3 and not torch.is_grad_enabled()):
+                and x.shape[2] == 1 and x.shape[1] == self.fcn_in.in_channels <= K.L.MAX_IN_FEAT
+                and not torch.is_grad_enabled()):
             if ROUTING.rt_one_launch and self._frame_desc_ok():
                 # the whole frame as ONE persistent launch (rt_fused.hip rt_frame_kernel)
                 return self._rt_frame(x)
@@ -429,8 +430,9 @@ class RtStreamBatch(StreamBatch):
         if model.normalization != "LayerNorm":
             raise RuntimeError("stgcn_amd: stream_batch supports LayerNorm online models only (BatchNorm online "
                                "layers are out of scope)")
-        if model.fcn_in.in_channels != 3:
-            raise RuntimeError(f"stgcn_amd: stream_batch needs in_feat == 3, got {model.fcn_in.in_channels}")
+        if not 1 <= model.fcn_in.in_channels <= K.L.MAX_IN_FEAT:
+            raise RuntimeError(f"stgcn_amd: stream_batch needs 1 <= in_feat <= {K.L.MAX_IN_FEAT}, got "
+                               f"{model.fcn_in.in_channels}")
         self._check_B(B)  # ahead of the shape limits, as every refusal's order was
         if not model._frame_desc_ok() or model.A.shape[-1] * model.fcn_in.out_channels > 7680:
             raise RuntimeError("stgcn_amd: stream_batch shape limits: 2 <= V <= 32, channels % 4 == 0 and <= 256, "
@@ -487,7 +489,7 @@ class RtStreamBatch(StreamBatch):
         m, B, V = self.model, self.B, self.V
         dev = m.A.device
         d = K.L.RtStreamsClipDesc()
-        d.B, d.T, d.V, d.L, d.C0, d.K, d.dtype = B, cap, V, d0.L, d0.C0, d0.K, d0.dtype
+        d.B, d.T, d.V, d.L, d.C0, d.K, d.dtype, d.F = B, cap, V, d0.L, d0.C0, d0.K, d0.dtype, d0.F
         for n in ("ln_w", "ln_b", "w_in", "b_in", "w_out", "b_out"):
             setattr(d, n, getattr(d0, n))
         for i in range(d0.L):

@@ -32,8 +32,9 @@ def ln_rows(t, C, V):
 
 
 def fill_heads(d, model, keep):
-    """The six head pointers of a per-frame descriptor (RtFrameDesc, RtStreamsDesc, CoStreamsDesc): norm_in, fcn_in,
-    fcn_out of ``model``."""
+    """The six head pointers and in_feat (F) of a per-frame or clip descriptor: norm_in, fcn_in, fcn_out of
+    ``model``."""
+    d.F = model.fcn_in.in_channels
     d.ln_w, d.ln_b = keep(LF._flat_ln(model.norm_in.weight)), keep(LF._flat_ln(model.norm_in.bias))
     d.w_in = keep(f32(model.fcn_in.weight).reshape(model.fcn_in.out_channels, -1))
     d.b_in = keep(f32(model.fcn_in.bias))
@@ -260,6 +261,7 @@ class StreamBatch:
 
     CLIP_MAX_T = None  # the most frames the subclass's clip entry takes per call
     clip_frames = 1024  # step_clip's scratch bound: B * (frames per chunk) stays at or below this
+    F = 3  # features per joint of the input frames; __init__ takes the model's in_feat
 
     @staticmethod
     def _check_B(B):
@@ -269,7 +271,7 @@ class StreamBatch:
     def __init__(self, model, B):
         self._check_B(B)
         K.L.require_device(model.A)
-        self.model, self.B, self.V = model, int(B), model.A.shape[-1]
+        self.model, self.B, self.V, self.F = model, int(B), model.A.shape[-1], model.fcn_in.in_channels
         self._all = torch.ones(self.B, dtype=torch.int32, device=model.A.device)
         self._full = torch.full((self.B,), 2 ** 30, dtype=torch.int32, device=model.A.device)  # lengths=None
         self.state, self._pack = [], None
@@ -310,12 +312,12 @@ class StreamBatch:
         import_streams(self.kind, self.B, self._state_dtype(), self.state, snap, streams, select, name)
 
     def step(self, x, active=None):
-        """x (B, 3, 1, V) -> (B, num_classes, 1).  ``active``: None (every stream steps), an int32 device tensor
+        """x (B, in_feat, 1, V) -> (B, num_classes, 1).  ``active``: None (every stream steps), an int32 device tensor
         [B] of codes (0 skip: state untouched, zero output row; 1 step; 2 restart then step) used as given with no
         host sync, or a bool tensor / Python list converted on the host (True = step)."""
-        B, V, name = self.B, self.V, type(self).__name__
-        if x.dim() != 4 or tuple(x.shape) != (B, 3, 1, V):
-            raise RuntimeError(f"stgcn_amd: {name}.step expects x of shape {(B, 3, 1, V)}, got {tuple(x.shape)}")
+        B, V, name, F = self.B, self.V, type(self).__name__, self.F
+        if x.dim() != 4 or tuple(x.shape) != (B, F, 1, V):
+            raise RuntimeError(f"stgcn_amd: {name}.step expects x of shape {(B, F, 1, V)}, got {tuple(x.shape)}")
         K.L.require_device(x)
         x = K._f32c(x)
         active = self._codes(active, self._all, x.device)
@@ -369,7 +371,7 @@ class StreamBatch:
         return clips[cap][0]
 
     def step_clip(self, x, active=None, lengths=None):
-        """x (B, 3, T, V), T >= 1 -> (B, num_classes, T) fp32: stream b consumes frames 0 .. n_b - 1, n_b =
+        """x (B, in_feat, T, V), T >= 1 -> (B, num_classes, T) fp32: stream b consumes frames 0 .. n_b - 1, n_b =
         clamp(lengths[b], 0, T).  Column t < n_b of stream b is what ``step`` would return for that frame, the frames
         fed one tick at a time from the stream's current state, and its state ends where those n_b ticks would have
         left it; columns t >= n_b, and every column of a skipped stream, are zero.  ``active`` as in ``step`` (code 2:
@@ -380,9 +382,9 @@ class StreamBatch:
         A stream's outputs and state are bit-identical whatever B, its slot, T, the other streams and the chunking into
         consecutive ``step_clip`` calls are.  ``step``, ``step_clip`` and ``reset`` mix freely.  Calls run in chunks of
         min(CLIP_MAX_T, clip_frames // B) frames (a power of two), which bounds the scratch."""
-        B, V, name = self.B, self.V, type(self).__name__
-        if x.dim() != 4 or x.shape[0] != B or x.shape[1] != 3 or x.shape[2] < 1 or x.shape[3] != V:
-            raise RuntimeError(f"stgcn_amd: {name}.step_clip expects x of shape ({B}, 3, T >= 1, {V}), got "
+        B, V, name, F = self.B, self.V, type(self).__name__, self.F
+        if x.dim() != 4 or x.shape[0] != B or x.shape[1] != F or x.shape[2] < 1 or x.shape[3] != V:
+            raise RuntimeError(f"stgcn_amd: {name}.step_clip expects x of shape ({B}, {F}, T >= 1, {V}), got "
                                f"{tuple(x.shape)}")
         for what, a in (("active", active), ("lengths", lengths)):
             if a is not None and (len(a) if not torch.is_tensor(a) else (a.shape[0] if a.dim() == 1 else -1)) != B:

@@ -43,6 +43,14 @@ stream_state: snapshots of live co-st-gcn streams (CoStreamBatch.export_state / 
           beside a captured torch.clone of the snapshot's bytes (the machine's copy rate at this size) and the
           torch-level composition (per stream and layer roll + copy_, the heads read back to the host) in the same run; rows
           appended to profiles/stream_state.jsonl.  Only with --only stream_state.
+infeat:   the input head at a runtime in_feat.  (a) No regression at in_feat 3: the rt-st-gcn and the co-st-gcn (Kt 9)
+          stream-batch tick at config 3's widths, V 25, B in {1, 64, 256}, fp32 and bf16, graph-replayed HIP-event
+          time.  (b) The reference's freezing-of-gait model (in_feat 6, the 7-node IMU graph, config 3's nine
+          layers): stream-batch ticks at B in {1, 64, 256, 1024}, and one stream per frame through Model.forward.
+          --tree DIR runs the same measurement on another checkout of the project (its package and its library, in
+          this process alone): the baseline is a checkout of the parent commit, run alternately with this one;
+          what that checkout refuses is recorded as refused.  Rows appended to profiles/infeat.jsonl.  Only with
+          --only infeat.
 streams:  config 3 as a stream batch (Model.stream_batch, stgcn_rt_streams): B in {1, 8, 64, 256, 1024} streams
           advanced one frame per launch, HIP-event device time over 200 graph-replayed ticks after the FIFOs have
           filled, beside the single-stream one-launch route (stgcn_rt_frame) graph-replayed in the same run: ms per
@@ -50,7 +58,7 @@ streams:  config 3 as a stream batch (Model.stream_batch, stgcn_rt_streams): B i
           bf16) are measured in the same process, interleaved per B, --stream-repeats times over; the rows are also
           appended to profiles/rt_streams.jsonl.  Only with --only streams.
 
-    python tools/bench_configs.py [--frames 2000] [--steps 10] [--only 3|5|ln|f1|co|ms|streams|co_streams|co_clip|co_streams_clip|rt_streams_clip|stream_state]
+    python tools/bench_configs.py [--frames 2000] [--steps 10] [--only 3|5|ln|f1|co|ms|infeat|streams|co_streams|co_clip|co_streams_clip|rt_streams_clip|stream_state]
 Prints one JSON line per config.
 """
 import argparse
@@ -238,6 +246,101 @@ def streams(P, dev, batches=(1, 8, 64, 256, 1024), repeats=1):
                                  "single_stream_one_launch_device_ms": round(single, 4),
                                  "ratio_vs_B_sequential": round(ms / (B * single), 4)})
     return rows
+
+
+def _imu_graph():
+    """The reference's 7-node IMU sensor graph (data/skeletons/imu_fogit_ABCD.json), from the graph fixtures."""
+    import numpy as np
+    g = np.load(os.path.join(ROOT, "tests", "golden", "graphs.npz"))
+    V, center = (int(v) for v in g["meta/imu_fogit_ABCD"])
+    return {"num_node": V, "edge": g["edge/imu_fogit_ABCD"].tolist(), "center": center}
+
+
+def infeat(P, dev, tree, repeat, emit, batches=(1, 64, 256), imu_batches=(1, 64, 256, 1024)):
+    """Rows of DESIGN 4.25 for one checkout (``tree``: its label) in one process, each handed to ``emit`` as it is
+    measured; see the module docstring."""
+    gen = torch.Generator(device=dev).manual_seed(3)
+    fill = 32  # > the 17-frame FIFOs of the stride-2 layers (kernel 9)
+
+    def row(**kw):
+        emit(dict(tree=tree, repeat=repeat, **kw))
+
+    with torch.no_grad():
+        # (a) in_feat 3: the shapes of profiles/rt_streams.jsonl
+        torch.manual_seed(0)
+        m = P.MODELS["rt-st-gcn"](rank=None, **dict(RT_ARCH, graph=P.PKU_MMD)).to(dev).eval()
+        m.prepare_benchmark(RT_ARCH)
+        for B in batches:
+            x = torch.randn(B, 3, 1, 25, device=dev, generator=gen)
+            for dtype in ("fp32", "bf16"):
+                sb = None
+                sb = m.stream_batch(B, dtype)
+                row(config="3 as a stream batch (stgcn_rt_streams), in_feat 3, V 25", dtype=dtype, B=B,
+                    tick_device_ms=round(_replay_ms(lambda: sb.step(x), fill), 4))
+        sb = m = None
+        for dtype in ("fp32", "bf16"):
+            arch = {"strategy": "spatial", "in_feat": 3, "stages": 1, "kernel": 9, "output_type": "logits",
+                    "normalization": "LayerNorm", "num_classes": 52, "graph": P.PKU_MMD,
+                    "st-gcn": dict(LAYERS, latency=False, importance=True, in_feat=3, stages=1, dilation=[1] * 9)}
+            torch.manual_seed(0)
+            mc = P.MODELS["co-st-gcn"](rank=None, **arch).to(dev).eval().set_compute_dtype(dtype)
+            for B in batches:
+                x = torch.randn(B, 3, 1, 25, device=dev, generator=gen)
+                sb = mc.stream_batch(B)
+                row(config="co-st-gcn as a stream batch (stgcn_co_streams), Kt 9, in_feat 3, V 25", dtype=dtype, B=B,
+                    tick_device_ms=round(_replay_ms(lambda: sb.step(x), fill), 4))
+                sb = None
+                torch.cuda.empty_cache()
+        mc = None
+        # (b) the reference's IMU model: in_feat 6, V 7
+        graph = _imu_graph()
+        V = graph["num_node"]
+        arch = dict(RT_ARCH, in_feat=6, num_classes=2, graph=graph)
+        arch["rt-st-gcn"] = dict(RT_ARCH["rt-st-gcn"], in_feat=6)
+        name = "rt-st-gcn imu_fogit_ABCD (in_feat 6, V 7, config 3's nine layers, LN, K=9)"
+        torch.manual_seed(0)
+        m = P.MODELS["rt-st-gcn"](rank=None, **arch).to(dev).eval()
+        m.prepare_benchmark(arch)
+        for B in imu_batches:
+            x = torch.randn(B, 6, 1, V, device=dev, generator=gen)
+            for dtype in ("fp32", "bf16"):
+                try:
+                    sb = None
+                    sb = m.stream_batch(B, dtype)
+                except RuntimeError as e:  # before the feature: refused on the host, nothing ran
+                    row(config=name + " as a stream batch", dtype=dtype, B=B, refused=str(e))
+                    continue
+                ms = _replay_ms(lambda: sb.step(x), fill)
+                row(config=name + " as a stream batch", dtype=dtype, B=B, tick_device_ms=round(ms, 4),
+                    frames_per_s=round(B / ms * 1e3, 1),
+                    note="V = 7 fills 7 of the 32 rows of the MFMA operand")
+        sb = None
+        # one stream, one frame per Model.forward call, eager: wall time per synchronised frame and device time of
+        # 200 back-to-back frames.  The route is the checkout's own: one persistent launch where the head takes
+        # in_feat 6, the generic layer kernels where it does not.
+        frames = torch.randn(264, 1, 6, 1, V, device=dev, generator=gen)
+        m.reset_state()
+        lat = []
+        for i in range(264):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            m(frames[i])
+            torch.cuda.synchronize()
+            lat.append(time.perf_counter() - t0)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for i in range(200):
+            m(frames[i])
+        e1.record()
+        torch.cuda.synchronize()
+        one = getattr(m, "_frame_pack", None) is not None
+        out = {"eager_p50_ms": round(1e3 * pct(lat[64:], 0.5), 4),
+               "eager_back_to_back_ms_per_frame": round(e0.elapsed_time(e1) / 200, 4)}
+        if one:  # the one-launch route captures as config 3's does
+            x1 = frames[0].clone()
+            out["graph_device_ms_per_frame"] = round(_replay_ms(lambda: m(x1), fill), 4)
+        row(config=name + ", one stream, one frame per call", dtype="fp32",
+            route="one persistent launch (stgcn_rt_frame)" if one else "generic layer kernels, frame by frame", **out)
 
 
 def config5(P, dev, steps, warmup):
@@ -843,8 +946,18 @@ def main():
     ap.add_argument("--ln-reps", type=int, default=3)
     ap.add_argument("--ln-route", choices=("both", "fused", "unfused"), default="both")
     ap.add_argument("--stream-repeats", type=int, default=3)
+    ap.add_argument("--tree", default=None, help="infeat: another checkout of the project to measure instead")
+    ap.add_argument("--label", default="branch", help="infeat: the rows' tree label")
+    ap.add_argument("--repeat", type=int, default=0, help="infeat: the rows' repeat index")
     args = ap.parse_args()
-    P = ge.load_package()
+    if args.tree:  # that checkout's package and library; this file only measures
+        import importlib.util
+        spec = importlib.util.spec_from_file_location("graft_entry_tree", os.path.join(args.tree, "__graft_entry__.py"))
+        other = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(other)
+        P = other.load_package()
+    else:
+        P = ge.load_package()
     dev = torch.device("cuda", 0)
     if args.only in (None, "3"):
         print(json.dumps(config3(P, dev, args.frames)), flush=True)
@@ -860,6 +973,12 @@ def main():
             print(json.dumps(ms_stage(P, dev, dtype)), flush=True)
         for dtype in ("fp32", "bf16"):
             print(json.dumps(msgcn_step(P, dev, dtype, min(args.steps, 5))), flush=True)
+    if args.only == "infeat":
+        with open(os.path.join(ROOT, "profiles", "infeat.jsonl"), "a") as f:
+            def emit(row):
+                print(json.dumps(row), flush=True)
+                f.write(json.dumps(row) + "\n")
+            infeat(P, dev, args.label, args.repeat, emit)
     if args.only == "streams":
         with open(os.path.join(ROOT, "profiles", "rt_streams.jsonl"), "a") as f:
             for row in streams(P, dev, repeats=args.stream_repeats):
